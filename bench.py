@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: bitonic sort of 2^30 uint32 keys (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N   (one process per GPU)
 
 A step = one full parallel_bitonic_sort (psort.cc:167) of the 2^30 keys that
@@ -15,14 +15,20 @@ the sort is out of place so every step sorts the same unsorted input.
 under `python -m torch.distributed.run --nproc-per-node N` as a child process
 BEFORE anything touches the GPU, and exits with the child's status.
 
-Rank 0 prints ONE JSON line with the metric, the per-kernel roofline of the
-dominant kernel (HIP events on the sort stream inside the timed region;
-algorithmic bytes = 2 * keys * 4 B per pass) and the CPU baseline: the
-reference's own parallel_bitonic_sort (oracle/_ref, compiled from the
-unmodified psort.cc) under mpirun on this host's cores, on the same workload.
-At N > 1 it adds per-stage exchange / merge-split times, the xGMI bytes and
-rate of every hypercube stage, and t1 / (P * tP) against a 1-GPU leg of the
-same keys run in the same job.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on
+rank 0: the metric and the per-kernel roofline of the dominant kernel (HIP
+events on the sort stream inside the timed region; algorithmic bytes =
+2 * keys * 4 B per pass); at N > 1 also the per-stage exchange / merge-split
+times and the xGMI bytes and rate of every hypercube stage, from the same
+events.  `--dump-outputs DIR` writes what the last timed step returned (each
+rank's sorted block, or a fixed seeded sample of it) as DIR/<name>.npy.
+
+`--full` adds everything that takes runs of its own: the CPU baseline (the
+reference's own parallel_bitonic_sort, oracle/_ref, compiled from the
+unmodified psort.cc, under mpirun on this host's cores, on the same workload;
+`--cpu-sweep` for other rank counts), at N > 1 the sample-sort timing (`alt`)
+and t1 / (P * tP) against a 1-GPU leg of the same keys run in the same job,
+and the PCIe-inclusive path (`--host-io`).
 """
 import argparse
 import faulthandler
@@ -43,6 +49,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 SEED = 0x5EED0003
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "psort_ref")
 MPIRUN = "/opt/conda/bin/mpirun"
+DUMP_KEYS = 1 << 21  # --dump-outputs: keys written in all (16 MiB as float64, 32 MiB as u64 halves)
 
 
 def parse_args(argv=None):
@@ -56,17 +63,24 @@ def parse_args(argv=None):
                          "uniform doubles in [0, 1)")
     ap.add_argument("--algo", choices=["bitonic", "sample"], default="bitonic",
                     help="bitonic = psort.cc:167 (the metric); sample = psort.cc:203-375 redesigned")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned as DIR/<name>.npy "
+                         "(float64): each rank's sorted block, or a fixed seeded sample of it with both "
+                         "ends when it holds more than 2^21 keys in all; u64 keys as _hi / _lo 32-bit halves")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (and "
+                         "--cpu-sweep), at N>1 the sample-sort timing and the 1-GPU leg, --host-io")
     ap.add_argument("--no-alt", action="store_true",
-                    help="N>1: skip the extra sample-sort timing reported under 'alt'")
+                    help="--full, N>1: skip the extra sample-sort timing reported under 'alt'")
     ap.add_argument("--no-t1", action="store_true",
-                    help="N>1: skip the 1-GPU leg that scaling_eff is computed against")
+                    help="--full, N>1: skip the 1-GPU leg that scaling_eff is computed against")
     ap.add_argument("--cpu-sample-logn", type=int, default=None,
-                    help="log2 keys of the CPU baseline sample (default: the workload, --logn)")
+                    help="--full: log2 keys of the CPU baseline sample (default: the workload, --logn)")
     ap.add_argument("--cpu-sweep", action="store_true",
-                    help="also time the reference at P = 1, 2, 4, ... cores on u32 and on its own f64 "
+                    help="--full: also time the reference at P = 1, 2, 4, ... cores on u32 and on its own f64 "
                          "workload (BASELINE.md section 3), reported under cpu_sweep")
     ap.add_argument("--cpu-sweep-logn", type=int, default=27)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--watchdog-s", type=float, default=1200.0,
                     help="a rank still running after this many seconds prints every thread's stack and "
                          "exits (1): a hang ends as an error, as the reference's alarm(540) does "
@@ -74,10 +88,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-kernel-events", action="store_true",
                     help="time without per-launch HIP events (roofline omitted)")
     ap.add_argument("--host-io", action="store_true",
-                    help="also time the PCIe-inclusive path (host keys -> misort_sort_host -> host "
+                    help="--full: also time the PCIe-inclusive path (host keys -> misort_sort_host -> host "
                          "keys), staged and overlapped vs one chunk; reported under 'host_io', "
                          "never as value")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full and (args.cpu_sweep or args.host_io):
+        ap.error("--cpu-sweep and --host-io are runs of their own: add --full")
+    return args
 
 
 # ------------------------------------------------------------------ launcher
@@ -325,18 +342,41 @@ def pass_rows(passes, traffic):
     return rows
 
 
+# ------------------------------------------------------------------ outputs
+def dump_indices(n, limit=DUMP_KEYS):
+    """Positions of an n-key output block that --dump-outputs writes: all of
+    them when they fit in `limit`, else both ends and a fixed (seeded) sample,
+    ascending -- the same positions in every run and every build."""
+    import numpy as np
+    if n <= limit:
+        return np.arange(n, dtype=np.int64)
+    idx = np.random.default_rng(SEED).integers(0, n, size=max(limit - 2, 0), dtype=np.int64)
+    return np.unique(np.concatenate((np.array([0, n - 1], dtype=np.int64), idx)))
+
+
+def dump_arrays(name, keys):
+    """{file stem: float64 array} of a numpy key array, exact for every dtype:
+    u32 and f64 as they are, u64 as its upper and lower 32-bit halves."""
+    import numpy as np
+    if keys.dtype == np.uint64:
+        return {f"{name}_hi": (keys >> np.uint64(32)).astype(np.float64),
+                f"{name}_lo": (keys & np.uint64(0xFFFFFFFF)).astype(np.float64)}
+    return {name: keys.astype(np.float64)}
+
+
 # -------------------------------------------------------------------- ranks
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
     if needs_launch(args):
-        # one process per GPU; this process never touches the GPU.  It runs the
-        # host-core baseline first (the reference under mpirun on this host's
-        # cores) and hands it to rank 0 in a file, so the N-GPU line carries it.
+        # one process per GPU; this process never touches the GPU.  Under
+        # --full it runs the host-core baseline first (the reference under
+        # mpirun on this host's cores) and hands it to rank 0 in a file, so the
+        # N-GPU line carries it.
         cmd = launch_command(argv, args.gpus, free_port())
         env = dict(os.environ, MASTER_ADDR="127.0.0.1")
         path = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.logn if args.cpu_sample_logn is None else args.cpu_sample_logn,
                                args.cpu_sweep, args.cpu_sweep_logn, args.dtype)
             fd, path = tempfile.mkstemp(prefix="misort_bench_cpu_", suffix=".json")
@@ -357,12 +397,12 @@ def main(argv=None):
     if world > 1 and args.gpus != world:
         sys.stderr.write(f"WARNING --gpus {args.gpus} but WORLD_SIZE {world}: running {world} ranks\n")
 
-    # The CPU baseline runs first, before this process touches the GPU, on
+    # The CPU baseline (--full) runs first, before this process touches the GPU, on
     # rank 0 at every N (the other ranks wait in the process-group setup):
     # the reference's parallel_bitonic_sort under mpirun on the host cores,
     # or the launcher parent's measurement of it when there was one.
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = load_cpu_json(os.environ.get(CPU_JSON_ENV))
         if cpu is None:
             cpu = cpu_baseline(args.logn if args.cpu_sample_logn is None else args.cpu_sample_logn,
@@ -468,6 +508,18 @@ def main(argv=None):
     xst = ctx.exchange_stats()
     errors = ctx.check_sort(d_out, loc)  # psort.cc:497-520 over all ranks
 
+    if args.dump_outputs:
+        # the block the last timed step left in d_out (later legs overwrite it)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        idx = dump_indices(loc, DUMP_KEYS // nranks)
+        bits = d_out[:loc].view(torch.int32 if key_bytes == 4 else torch.int64)
+        got = bits[torch.from_numpy(idx).cuda()].cpu().numpy()
+        got = got.view({"u32": np.uint32, "u64": np.uint64, "f64": np.float64}[args.dtype])
+        name = "sorted_keys" if nranks == 1 else f"sorted_keys_rank{rank}"
+        for stem, arr in dump_arrays(name, got).items():
+            np.save(os.path.join(args.dump_outputs, stem + ".npy"), arr)
+        del bits, got
+
     stage_rows = None
     if stages:
         sched = misort.schedule(nranks, rank)
@@ -488,7 +540,7 @@ def main(argv=None):
                 "xgmi_GBs": b_max / (x_max * 1e-3) / 1e9 if x_max > 0 else None})
 
     alt = None
-    if nranks > 1 and args.algo == "bitonic" and not args.no_alt:
+    if args.full and nranks > 1 and args.algo == "bitonic" and not args.no_alt:
         # the redesigned sample sort (one RCCL all-to-all) on the same input, same contract
         ts = timed("sample", args.steps)
         alt = {"sample_sort": {"value": n_total * args.steps / ts / 1e9, "unit": "Gkeys/s",
@@ -498,7 +550,7 @@ def main(argv=None):
                                        "merge tree, rebalance to the reference layout"}}
 
     t1 = None
-    if nranks > 1 and not args.no_t1:
+    if args.full and nranks > 1 and not args.no_t1:
         # 1-GPU leg: rank 0 sorts ALL n_total keys alone on its GPU (a P = 1
         # context), same keys, same steps; scaling_eff = t1 / (P * tP)
         barrier()
@@ -525,7 +577,7 @@ def main(argv=None):
         barrier()
 
     host_io = None
-    if args.host_io:
+    if args.full and args.host_io:
         # host keys of the same workload; sorted through the pinned staging pipeline
         h_in = d_in[:loc].cpu().numpy()
         h_in = h_in if args.dtype == "f64" else h_in.view(np.uint32 if key_bytes == 4 else np.uint64)

@@ -6,4 +6,4 @@ timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$O/s
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 900 python3 -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider \
   > "$O/pytest.log" 2>&1; rc=$?; echo "pytest rc $rc"; grep -E "FAILED|passed|failed" "$O/pytest.log" | tail -12; fatal $rc pytest
-timeout -k 10 400 python3 -u bench.py > "$O/bench.json" 2> "$O/bench.err"; rc=$?; echo "bench rc $rc"; tail -c 3000 "$O/bench.json"; fatal $rc bench
+timeout -k 10 400 python3 -u bench.py --full > "$O/bench.json" 2> "$O/bench.err"; rc=$?; echo "bench rc $rc"; tail -c 3000 "$O/bench.json"; fatal $rc bench

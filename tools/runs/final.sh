@@ -30,7 +30,7 @@ if [[ $P == *" suite "* ]]; then
   echo "pytest rc $rc: $(tail -1 "$O/gpu_suite.log")"; [ $rc -ne 0 ] && grep -E "FAILED|Error" "$O/gpu_suite.log" | head; fatal $rc pytest
 fi
 if [[ $P == *" bench "* ]]; then
-  timeout -k 10 400 python3 -u bench.py > "$O/bench_default.json" 2> "$O/bench_default.err"; rc=$?
+  timeout -k 10 400 python3 -u bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"; rc=$?
   [ $rc -ne 0 ] && tail -5 "$O/bench_default.err"; fatal $rc bench; line "$O/bench_default.json"
 fi
 if [[ $P == *" prof "* ]]; then
