@@ -361,7 +361,13 @@ class Context:
         out = torch.empty_like(local) if out is None else out
         if in_place_tail:
             if out.data_ptr() != local.data_ptr():
-                out[:local.numel()].copy_(local)
+                out[:local.numel()].copy_(local)  # on torch's current stream
+                cur = torch.cuda.current_stream(local.device)
+                if stream is not None and int(stream) != cur.cuda_stream:
+                    # the merge on `stream` starts after the copy
+                    done = torch.cuda.Event()
+                    done.record(cur)
+                    torch.cuda.ExternalStream(int(stream), device=local.device).wait_event(done)
             _check(lib().misort_merge_split_tail(self._h, _dtype_of(local), _ptr(out), local.numel(),
                                                  _ptr(recv), recv.numel(), int(keep_max), self._stream(stream)))
             return out

@@ -164,6 +164,38 @@ def test_merge_split_tail(ctx, case, na, nb, keep_max, kd):
 
 
 @pytest.mark.parametrize("keep_max", [0, 1])
+@pytest.mark.parametrize("kd", [np.uint32, np.float64])
+def test_merge_split_tail_on_another_stream(ctx, kd, keep_max):
+    """compare_split(in_place_tail=True, stream=s): the copy of `local` into
+    `out` runs on torch's current stream, the merge on s; the merge must wait
+    for the copy.  The current stream is kept busy (a 2^26-key sort queued just
+    before the call), so a merge that does not wait reads `out` before the copy
+    lands.  `out` starts as zeros -- a sorted block, so the kernels'
+    preconditions hold whatever they read -- and the late copy then overwrites
+    the merge's result: the output differs from the oracle's."""
+    na, nb = 100000, 4096
+    a = O.local_sort((1 + O.splitmix(na * 5 + 2, na, np.uint64) % (1 << 30)).astype(kd))
+    b = O.local_sort((1 + O.splitmix(nb * 3 + 9, nb, np.uint64) % (1 << 30)).astype(kd))
+    want = O.compare_split(a, b, keep_max)
+    assert not np.array_equal(want, a)  # the merge changes the block
+    iv = np.uint64 if kd == np.float64 else kd
+    d_a, d_b = to_dev(a), to_dev(b)
+    # the context's scratch buffers grow on first use, and growing them waits
+    # for the device: one call on the current stream first
+    warm = ctx.compare_split(d_a, d_b, keep_max, in_place_tail=True)
+    np.testing.assert_array_equal(to_host(warm, kd).view(iv), want.view(iv))
+    out = to_dev(np.zeros_like(a))
+    busy = torch.randint(0, 1 << 30, (1 << 26,), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    busy.sort()
+    ctx.compare_split(d_a, d_b, keep_max, out=out, stream=ctx.native_stream, in_place_tail=True)
+    ctx.synchronize()
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(to_host(out, kd).view(iv), want.view(iv))
+    np.testing.assert_array_equal(to_host(d_a, kd).view(iv), a.view(iv))
+
+
+@pytest.mark.parametrize("keep_max", [0, 1])
 def test_merge_split_f64(ctx, keep_max):
     a = O.local_sort(O.generate_f64(5001))
     b = O.local_sort(O.generate_f64(4999) * 0.5)
