@@ -1005,7 +1005,7 @@ hipError_t local_sort_impl(const K* in, K* out, int64_t n, bool ord_in, K* scrat
     int fence_phase = 0;  // multi-way passes: fence buffer holding the next pass's fences
     // the multi-way passes' fence stride: 64-key fences (runsk_fg6.hip) for
     // large sorts, every pass of one sort the same build
-    const bool fg6 = mergek_fence_log2(n, (int)sizeof(K)) == 6;
+    const MergekBuild& mk = mergek_build(mergek_fence_log2(n, (int)sizeof(K)));
     // the SORT pass writes the first multi-way pass's fences (no gather pass)
     // unless it runs chunk by chunk (host staging)
     const bool sort_fences = np > 1 && ps[1].kind == KIND_RUNSK && ps[1].hi == LT && !(io && io->before_first);
@@ -1025,18 +1025,11 @@ hipError_t local_sort_impl(const K* in, K* out, int64_t n, bool ord_in, K* scrat
             // by the HookScope marker above; binding there too would record it
             // twice, from a stale start); a marker hook nests k_mergek's record
             LaunchHook* kh = bind || !(hook && hook->binds()) ? hook : nullptr;
-            hipError_t e;
-            if constexpr (sizeof(K) == 8) {
-                // the last pass stores IEEE double bits itself
-                const bool oo = ord_out && i == np - 1;
-                e = fg6 ? merge_levelk_fg6(src, dst, n, p.hi, p.R, s, fence_phase, !prevk, lk_next, kh, oo)
-                        : merge_levelk(src, dst, n, p.hi, p.R, s, fence_phase, !prevk, lk_next, kh, oo);
-                if (oo && e == hipSuccess) ord_out = false;
-            } else {
-                e = fg6 ? merge_levelk_fg6(src, dst, n, p.hi, p.R, s, fence_phase, !prevk, lk_next, kh)
-                        : merge_levelk(src, dst, n, p.hi, p.R, s, fence_phase, !prevk, lk_next, kh);
-            }
+            // the last pass stores IEEE double bits itself (ord_out: u64 only)
+            const bool oo = ord_out && i == np - 1;
+            const hipError_t e = mk.merge_levelk(src, dst, n, p.hi, p.R, s, fence_phase, !prevk, lk_next, kh, oo);
             if (e != hipSuccess) return e;
+            if (oo) ord_out = false;
             fence_phase ^= 1;
             src = dst;
             continue;
@@ -1067,11 +1060,11 @@ hipError_t local_sort_impl(const K* in, K* out, int64_t n, bool ord_in, K* scrat
             if (bind) (void)hook->bind(KIND_TILE_SORT, -1, bytes, &ea, &eb);
             void* f = nullptr;
             if (i == 0 && sort_fences) {
-                f = fg6 ? mergek_fence_buffer_fg6(n, (int)sizeof(K), 0, s) : mergek_fence_buffer(n, (int)sizeof(K), 0, s);
+                f = mk.fence_buffer(n, (int)sizeof(K), 0, s);
                 if (!f) return hipErrorOutOfMemory;
             }
             // flk: the first pass's lk and, above bit 8, the fence stride
-            launch_sort<K>(src, dst, n, ord_in, s, LT, f, f ? ps[1].R | ((fg6 ? 6 : MERGEK_FENCE_LOG2) << 8) : 0, ea, eb);
+            launch_sort<K>(src, dst, n, ord_in, s, LT, f, f ? ps[1].R | (mk.fence_log2 << 8) : 0, ea, eb);
         }
         src = dst;
     }
@@ -1107,7 +1100,7 @@ hipError_t run_pass(const K* in, K* out, int64_t n, int kind, int hi, int R, int
     (void)flip;
     if (n <= 0) return hipSuccess;
     if (kind == KIND_RUNS) return merge_level<K>(in, out, n, hi, s);
-    if (kind == KIND_RUNSK) return merge_levelk(in, out, n, hi, R > 0 ? R : 2, s, 0, true, 0);
+    if (kind == KIND_RUNSK) return mergek_build(MERGEK_FENCE_LOG2).merge_levelk(in, out, n, hi, R > 0 ? R : 2, s, 0, true, 0);
     if (kind != KIND_TILE_SORT) return hipErrorInvalidValue;
     launch_sort<K>(in, out, n, false, s, hi + 1 == SORT_LT_MERGE ? SORT_LT_MERGE : KT<K>::LT);
     return hipGetLastError();

@@ -133,24 +133,6 @@ template <typename K>
 hipError_t merge_level(const K* src, K* dst, int64_t n, int lw, hipStream_t s, int64_t o0 = 0, int64_t o1 = 0,
                        LaunchHook* hook = nullptr);
 
-// lk merge levels in one HBM pass (runsk.hip, u32 and u64, lk = 1..4): src holds
-// ascending runs of 2^lw keys, dst gets ascending runs of 2^(lw+lk) (2^lk-way
-// merge of each group of runs; the last group may be short).  Chunks are cut
-// at fences (every 128th key of a run): `phase` selects which of two
-// per-stream fence buffers holds this pass's fences; gather = build them from
-// src first (the pass after a non-multi-way pass); lk_next > 0 = write the
-// fences of the next multi-way pass (runs of 2^(lw+lk), groups of 2^lk_next)
-// into the other buffer.  SORT_LT_MERGE <= lw, lw + lk <= 30; src != dst; buffers 16-byte
-// aligned.
-hipError_t merge_levelk(const uint32_t* src, uint32_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
-                        bool gather, int lk_next, LaunchHook* hook = nullptr);
-// u64 keys: the same with 128-bit fences (key << 64 | run/position tag);
-// 13 <= lw, lw + lk <= 29.
-// ord_out: the pass is the sort's last (lk_next = 0) and writes IEEE double
-// bits (f64_of_ord in its stores: no separate back-conversion sweep).
-hipError_t merge_levelk(const uint64_t* src, uint64_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
-                        bool gather, int lk_next, LaunchHook* hook = nullptr, bool ord_out = false);
-int64_t mergek_chunks(int64_t n, int lw, int lk, int key_bytes);
 // Fence stride of the multi-way passes (log2 keys).
 constexpr int MERGEK_FENCE_LOG2 = 7;  // runsk_fg6.hip: 6 (fence stride 256 measured equal to 128, profiles/r02)
 // log2 keys of the u32 SORT tiles (bitonic.h).  15: 1024 lanes, one
@@ -159,21 +141,48 @@ constexpr int MERGEK_FENCE_LOG2 = 7;  // runsk_fg6.hip: 6 (fence stride 256 meas
 // The plan picks per size (sort_tile_u32); u32 multi-way passes take runs of
 // 2^14 and up.
 constexpr int SORT_LT_U32 = 15, SORT_LT_MERGE = 14;
-// The per-stream fence buffer `phase` of a multi-way pass over n keys (the
-// one merge_levelk reads with that phase), for a SORT pass that writes the
-// first pass's fences itself; null on allocation failure.
-void* mergek_fence_buffer(int64_t n, int key_bytes, int phase, hipStream_t s);
-void mergek_release(hipStream_t s);
-int mergek_take_error(hipStream_t s);
-// The same entry points of the 64-key-fence build (runsk_fg6.hip).
-hipError_t merge_levelk_fg6(const uint32_t* src, uint32_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
-                            bool gather, int lk_next, LaunchHook* hook = nullptr);
-hipError_t merge_levelk_fg6(const uint64_t* src, uint64_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
-                            bool gather, int lk_next, LaunchHook* hook = nullptr, bool ord_out = false);
-int64_t mergek_chunks_fg6(int64_t n, int lw, int lk, int key_bytes);
-void* mergek_fence_buffer_fg6(int64_t n, int key_bytes, int phase, hipStream_t s);
-void mergek_release_fg6(hipStream_t s);
-int mergek_take_error_fg6(hipStream_t s);
+
+// The multi-way merge passes (runsk.hip) are built once per fence stride; each
+// build exports this one handle.
+struct MergekBuild {
+    int fence_log2;  // a fence every 2^fence_log2 keys of a run
+    // lk merge levels in one HBM pass (u32 and u64, lk = 1..4): src holds
+    // ascending runs of 2^lw keys, dst gets ascending runs of 2^(lw+lk) (2^lk-way
+    // merge of each group of runs; the last group may be short).  Chunks are cut
+    // at fences: `phase` selects which of two per-stream fence buffers holds this
+    // pass's fences; gather = build them from src first (the pass after a
+    // non-multi-way pass); lk_next > 0 = write the fences of the next multi-way
+    // pass (runs of 2^(lw+lk), groups of 2^lk_next) into the other buffer.
+    // u32: SORT_LT_MERGE <= lw, lw + lk <= 30.  u64: 128-bit fences (key << 64 |
+    // run/position tag), 13 <= lw, lw + lk <= 29.  src != dst; buffers 16-byte
+    // aligned.  ord_out (u64 only): the pass is the sort's last (lk_next = 0) and
+    // writes IEEE double bits (f64_of_ord in its stores: no separate sweep).
+    hipError_t (*levelk_u32)(const uint32_t* src, uint32_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
+                             bool gather, int lk_next, LaunchHook* hook, bool ord_out);
+    hipError_t (*levelk_u64)(const uint64_t* src, uint64_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
+                             bool gather, int lk_next, LaunchHook* hook, bool ord_out);
+    // The per-stream fence buffer `phase` of a pass over n keys (the one
+    // merge_levelk reads with that phase), for a SORT pass that writes the first
+    // pass's fences itself; null on allocation failure.
+    void* (*fence_buffer)(int64_t n, int key_bytes, int phase, hipStream_t s);
+    // 1 if a pass on stream s rejected a chunk since the last call (the stream
+    // is synchronised), else 0; negative on a HIP error.
+    int (*take_error)(hipStream_t s);
+    // Frees the fence and planning scratch kept for stream s on the current device.
+    void (*release)(hipStream_t s);
+
+    hipError_t merge_levelk(const uint32_t* src, uint32_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
+                            bool gather, int lk_next, LaunchHook* hook = nullptr, bool ord_out = false) const {
+        return levelk_u32(src, dst, n, lw, lk, s, phase, gather, lk_next, hook, ord_out);
+    }
+    hipError_t merge_levelk(const uint64_t* src, uint64_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
+                            bool gather, int lk_next, LaunchHook* hook = nullptr, bool ord_out = false) const {
+        return levelk_u64(src, dst, n, lw, lk, s, phase, gather, lk_next, hook, ord_out);
+    }
+};
+// The build for a fence stride, and every build's stride (runsk.hip, runsk_fg6.hip).
+const MergekBuild& mergek_build(int fence_log2);
+constexpr int MERGEK_BUILDS[2] = {MERGEK_FENCE_LOG2, 6};
 // The fence stride (log2 keys) the local sort of n keys uses: 6 (runsk_fg6)
 // from 2^MISORT_FENCE_FG6_MIN keys (u32: never by default, u64: 29), else MERGEK_FENCE_LOG2.
 int mergek_fence_log2(int64_t n, int key_bytes);

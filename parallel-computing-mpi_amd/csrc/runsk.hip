@@ -37,6 +37,9 @@
 // (FM + K) * FG = CAP keys and FM * FG on average.  The first multi-way pass
 // after the SORT tile gathers its fences from the runs (k_fence_gather);
 // later passes read the fences the previous pass wrote.
+//
+// The host side -- what a pass decides before it launches -- is mergek_plan.h;
+// merge_pass below turns that plan into launches.
 #include "kernels.h"
 #include "lds_merge.h"
 
@@ -47,24 +50,16 @@ namespace misort {
 namespace {
 
 // The fence stride: MERGEK_FENCE_LOG2 (kernels.h), or MISORT_RUNSK_FGL in the
-// second build of this file (runsk_fg6.hip: 64-key fences, its entry points
-// suffixed by MISORT_RUNSK_FN).
+// second build of this file (runsk_fg6.hip: 64-key fences).  Each build defines
+// one MergekBuild (kernels.h) in place of named entry points.
 #ifndef MISORT_RUNSK_FGL
 #define MISORT_RUNSK_FGL MERGEK_FENCE_LOG2
 #endif
-#ifndef MISORT_RUNSK_FN
-#define MISORT_RUNSK_FN(x) x
-#endif
-constexpr int FG_LOG2 = MISORT_RUNSK_FGL;
-constexpr int64_t FG = (int64_t)1 << FG_LOG2;  // fence stride (keys)
-typedef unsigned __int128 u128;
+// the chunk shapes (KTr, Shape, Desc), the group geometry (Geo), the knobs and
+// the host-side plan of a pass (plan_pass), as host-only code
+#include "mergek_plan.h"
+static_assert(KTr<uint32_t>::LW_MIN == SORT_LT_MERGE, "u32 multi-way passes take the smaller SORT tile's runs");
 
-// The first fence merge levels of a pass as LDS merge levels (k_fence_merge)
-// when the pass has at least FENCE_MERGE_MIN_BLOCKS sub-groups; else ranks by
-// binary searches (k_fence_lds), which can split a sub-group over several
-// blocks.  Measured (profiles/r03/ab3): 2^30 u32 66.5 -> 67.0 Gkeys/s, 2^26
-// 61.5 -> 62.1; at 2^24 (64 and 16 sub-groups) the merge was slower.
-constexpr int64_t FENCE_MERGE_MIN_BLOCKS = 128;
 // bytes of the aligned window k_bounds reads around its interpolated guess
 // (64: u32 passes -1..-10 us, u64 +2 us, profiles/r05/plan/bl64_ab.txt)
 constexpr int BOUNDS_LINE = 128;
@@ -78,108 +73,6 @@ constexpr int BOUNDS_LINE = 128;
 // (merge_chain: the two-key chain measured equal in the tile, -6 % in the
 // passes, profiles/r05/mergek/u64_chain_ab.txt); zero words below the A
 // sequences for the two-key chain (profiles/r05/zwpt).
-
-// Per key type: the fence type (key bits above 32 bits of run and position),
-// the chunk workgroup (NT lanes x IT keys: CAP keys a chunk at most), the
-// workgroups per CU the LDS tile allows, and the largest fence sub-group
-// merged in LDS (64 KiB).
-template <typename KEY>
-struct KTr;
-// u32, 2..8-way passes: 512 lanes x 18 outputs, 8960-key chunks (the largest
-// the 18-output level layout fits: CAP + 4 (G + QA) <= 9216; 8192 before: 2^24
-// +1.5 %, 2^28 +0.8 %, profiles/r04/chunk32), four workgroups per CU; 22
-// outputs per lane at three per CU measured slower (profiles/r06/plan/fg6_ab.txt).
-// 16-way passes: larger chunks.  A chunk holds FM * FG = CAP - K * FG keys on
-// average, so at K = 16 a quarter of an 8192-key chunk's lanes idle.  Round
-// 4: 22 outputs per lane (CAP 10752, three workgroups per CU) measured 2^30
-// 68.9 -> 69.8 Gkeys/s; 20 or 24 per lane were slower -- an EVEN half (IT / 2
-// = 10 or 12) puts the lanes' chain pointers, IT / 2 apart, on a few banks.
-// Round 6: 26 outputs per lane (IT / 2 = 13, odd) and the LDS sized by the
-// larger of the segments and the level outputs (not their sum): CAP 12864,
-// the largest the 26-output level layout holds (CAP + 8 (G + QA) <= 512 * 26),
-// still three workgroups per CU (53.4 KB); 2^30 k_mergek 2154 -> 2049 us,
-// 81.6 -> 84.4 Gkeys/s, 2^28 82.2 -> 84.6 (profiles/r06/mergek/it26_ab.txt);
-// 768 or 640 lanes at two workgroups per CU were slower (nt_ab.txt).  Load rows
-// of 128 keys (the descriptor holds 8 bytes per row; 64 -> 128 halved it:
-// 2^30 pass 2569 -> 2547 us, profiles/r05/plan/rw_ab.txt).
-template <>
-struct KTr<uint32_t> {
-    typedef uint64_t F;
-    static constexpr int NT = 512, IT = 18, CAP = 8960, WG_PER_CU = 4;
-    static constexpr int IT16 = 26, CAP16 = 12864, WG16 = 3;
-    // the chunk shape of a pass of lk levels
-    static constexpr bool big(int lk) { return lk == 4; }
-    static constexpr int it(int lk) { return big(lk) ? IT16 : IT; }
-    // (k_fence_counts keeps 8-bit per-chunk counts: at most 255 + K fences of FG
-    // keys a chunk, a bound only the 64-key build can reach)
-    static constexpr int cap16() { return CAP16 < (255 + 16) * FG ? CAP16 : (255 + 16) * (int)FG; }
-    static constexpr int cap(int lk) { return big(lk) ? cap16() : CAP; }
-    static constexpr int wg(int lk) { return big(lk) ? WG16 : WG_PER_CU; }
-    static constexpr int FL_LDS = 13;                       // 8192 fences = 64 KiB
-    static constexpr int LW_MIN = SORT_LT_MERGE, LWK_MAX = 30;  // runs >= the smaller SORT tile; 32-bit row offsets
-};
-// The u64 chunk shape: 18 outputs per lane and the largest capacity whose
-// level layout fits 512 x 18 slots (CAP + 8 (G + QA) <= 9216): 8832 keys
-// (69 fences of 128) instead of 8192 measured 2^29 u64 35.4 -> 36.5-36.7
-// Gkeys/s, k_mergek 2.46 -> 2.33 ms per pass, 2^26 +2.2 %; 9216 keys at 20 per
-// lane was slower (profiles/r04/chunk64).  The 64-key build (runsk_fg6.hip)
-// takes 8896 (139 fences of 64): k_mergek -5 us per 2^29 pass
-// (profiles/r05/mergek/cap_ab.txt).
-template <>
-struct KTr<uint64_t> {
-    typedef u128 F;
-    static constexpr int NT = 512, IT = 18, WG_PER_CU = 2;
-    static constexpr int CAP = FG_LOG2 == 6 ? 8896 : 8832;  // ~69 KiB of keys: two tiles per CU, 4 waves per SIMD
-    static constexpr int FL_LDS = 12;    // 4096 fences = 64 KiB
-    static constexpr int LW_MIN = 13, LWK_MAX = 29;  // runs >= the u64 SORT tile; 32-bit row offsets
-    static constexpr int it(int) { return IT; }
-    static constexpr int cap(int) { return CAP; }
-    static constexpr int wg(int) { return WG_PER_CU; }
-};
-
-// Every sequence an in-LDS merge reads is followed by G words of MAX
-// (sentinels), so a merge chain needs no end checks: it reads at most IT words
-// past an exhausted sequence.  Each level places its pairs' outputs at lane
-// boundaries past the previous pair's sentinels (no lane straddles two pairs).
-constexpr int PAD = 4;  // keys below the tile: a co-rank probe may read index -1
-
-constexpr int SCAN_NT_MAX = 256;  // chunks per fence-count block (SCAN_NT below)
-
-template <typename KEY, int LK>
-struct Shape {
-    typedef KTr<KEY> T;
-    // the merge chain of the in-LDS levels: two keys per read (u32), one (u64)
-    static constexpr int CH = sizeof(KEY) == 4 ? 1 : 0;
-    static constexpr int NT = T::NT, IT = T::it(LK), CAP = T::cap(LK);
-    static constexpr int MAXR = CAP / 2;  // co-rank range bound: min(LA, LB) <= CAP / 2
-    // zero words below the A sequences (co_rank without its i == lo test; the
-    // two-key chain): the last of the G words after a sequence holds the next
-    // one's, so G exceeds the keys a chain reads past a sequence (IT for the
-    // two-key chain, IT + 1 for the one-key chain)
-    static constexpr bool ZW = CH == 1;
-    static constexpr int G = IT + 1;
-    static constexpr int QA = IT;  // level outputs start at lane boundaries
-    static_assert(IT % 2 == 0, "outputs stored as aligned pairs");
-    // LDS slot of segment q (o = its first chunk position)
-    __device__ __host__ static int seg(int o, int q) { return o + q * G; }
-    static constexpr int K = 1 << LK, LKS = LK;
-    static constexpr int FM = CAP / (int)FG - K;   // fences per chunk, worst case (merge_pass cuts at more)
-    static constexpr int RW = LK == 4 ? 128 : (LK == 3 || NT % 256) ? 128 : 256;  // load row: RW keys of one segment
-    static constexpr int NR = NT / RW;             // row parts: waves [p*RW/64, (p+1)*RW/64) load part p
-    // load slots per lane: enough rows for CAP keys in K segments
-    static constexpr int LS_ROWS = ((CAP + RW - 1) / RW + K + NR - 1) / NR;
-    static constexpr int LS = ((IT + 1) & ~1) <= LS_ROWS ? LS_ROWS : ((IT + 1) & ~1);
-    static constexpr int NROWS = LS * NR;           // lane slot j of part p holds row j * NR + p
-    // the tile holds the chunk's segments with their sentinels (CAP + K G) and
-    // every level's outputs (<= NT IT slots by the level layout, + G sentinels)
-    static constexpr int NB_EXT = CAP + K * G > NT * IT + G ? CAP + K * G : NT * IT + G;
-    static constexpr int LDS_KEYS = PAD + NB_EXT + 16;
-    static_assert(FM > 0 && FM < 256 && SCAN_NT_MAX * FM < 65536,
-                  "fence stride vs chunk (k_fence_counts keeps 8-bit counts and 16-bit block prefixes)");
-    static_assert(CAP <= (NROWS - K) * RW, "segment rows: ceil(l_r / RW) summed over K segments");
-    static_assert(CAP + (K / 2) * (G + QA) <= NT * IT, "level layout: pairs at lane boundaries");
-    static_assert(LDS_KEYS < 65536, "LDS key index of a row fits 16 bits");
-};
 
 // fence <-> (key, tag): tag = run << (32 - lk) | position / FG, the low 32 bits
 template <typename KEY>
@@ -197,84 +90,6 @@ __device__ __forceinline__ auto fkey(F f) {
 template <typename F>
 __device__ __forceinline__ uint32_t ftag(F f) {
     return (uint32_t)f;
-}
-
-// Group geometry of the pass: groups of K runs of W keys; run r of group g
-// starts at g*KW + r*W and holds clamp(n - start, 0, W) keys.
-struct Geo {
-    int64_t n;
-    int lw, lk, fm;
-    int64_t nfull;  // full groups
-    int64_t kf;     // chunks per full group
-    __device__ __host__ int K() const { return 1 << lk; }
-    __device__ __host__ int64_t W() const { return (int64_t)1 << lw; }
-    __device__ __host__ int64_t base(int64_t g) const { return g << (lw + lk); }
-    __device__ __host__ int64_t run_len(int64_t g, int r) const {
-        const int64_t rest = n - (base(g) + r * W());
-        return rest <= 0 ? 0 : (rest < W() ? rest : W());
-    }
-    __device__ __host__ int64_t nfences(int64_t g) const {
-        const int64_t glen = (n - base(g)) < K() * W() ? n - base(g) : K() * W();
-        return (glen + FG - 1) >> FG_LOG2;
-    }
-    // a group's fences and chunks are < 2^31: a 32-bit division
-    __device__ __host__ int64_t nchunks(int64_t g) const {
-        return g < nfull ? kf : (int64_t)((uint32_t)(nfences(g) + fm - 1) / (uint32_t)fm);
-    }
-    // bounds slot of chunk t of group g (each group has nchunks + 1 slots)
-    __device__ __host__ int64_t slot(int64_t g, int64_t t) const {
-        return g < nfull ? g * (kf + 1) + t : nfull * (kf + 1) + t;
-    }
-};
-
-// fm = 0: the worst-case bound, (fm + K) * FG <= CAP
-template <typename KEY>
-Geo make_geo(int64_t n, int lw, int lk, int fm = 0) {
-    Geo geo{n, lw, lk, fm > 0 ? fm : KTr<KEY>::cap(lk) / (int)FG - (1 << lk), 0, 0};
-    geo.nfull = n >> (lw + lk);
-    geo.kf = ((((int64_t)1 << (lw + lk)) >> FG_LOG2) + geo.fm - 1) / geo.fm;
-    return geo;
-}
-
-// The capacity split's fences per chunk above the worst-case bound (merge_pass).
-// A chunk's size is FM * FG plus 2K window offsets of up to FG each, which
-// nearly cancel on spread keys (sigma ~ FG sqrt(2K / 12), 1.6 FG at K = 16):
-// 9 fences more at K = 16 (4.6 sigma of headroom with 128-key fences) and 3 at
-// K = 8 (4.3 sigma) keep splits to about one per few 2^30 passes on spread
-// keys -- a split's serial latency (k_split_desc) and its halves' merge sit on
-// the pass's critical path, so rarer splits beat fuller chunks here: 12 fences
-// more (2.8 sigma, ~0.3 % of chunks) measured slower than none at 2^28
-// (profiles/r06/mergek/split_ab.txt).  (env MISORT_MK_FM_ADD: one value
-// for every unfused pass, 0 = off), clamped so a half chunk still fits --
-// ceil(fm / 2) + K fences of FG keys <= CAP -- and fm <= 255 (k_fence_counts'
-// 8-bit counts).
-template <typename KEY, int LK>
-int split_fm_add() {
-    static const int env = getenv("MISORT_MK_FM_ADD") ? atoi(getenv("MISORT_MK_FM_ADD")) : -1;
-    // u64: equal kernel time, +25 us of split overhead per 2^29 pass (split_ab.txt): off
-    const int want = env >= 0 ? env : sizeof(KEY) == 8 ? 0 : LK == 4 ? 9 : LK == 3 ? 3 : 0;
-    const int K = 1 << LK, cap = KTr<KEY>::cap(LK), fm0 = cap / (int)FG - K;
-    int fm = fm0 + (want > 0 ? want : 0);
-    while (fm > fm0 && ((fm + 1) / 2 + K) * (int)FG > cap) --fm;
-    if (fm > 255) fm = 255;
-    return fm > fm0 ? fm - fm0 : 0;
-}
-
-// A group whose fence count lies just above a multiple of fm ends in a nearly
-// empty chunk (2^30 u32 pass 1: 2048 fences a group, fm 93 -> 23 chunks, the
-// last of 2 fences): up to FM_BALANCE fences more per chunk when that saves
-// the group a chunk, within the split's bound (halves fit, 8-bit counts), and
-// only where that chunk is >= 1/BAL_NC_MAX of the group's: 2^30 +0.35 %; on
-// every pass (+1 fence a chunk, more splits for 1 chunk in 250) 2^27 -1 %
-// (profiles/r06/mergek/balance_ab.txt).
-constexpr int FM_BALANCE = 3, BAL_NC_MAX = 32;
-template <typename KEY, int LK>
-int balance_fm(int fm, int64_t gf) {
-    const int K = 1 << LK, cap = KTr<KEY>::cap(LK);
-    const int64_t nc = gf / fm;
-    if (nc < 1 || nc > BAL_NC_MAX || nc * fm == gf) return fm;
-    const int fm2 = (int)((gf + nc - 1) / nc);
-    return fm2 <= fm + FM_BALANCE && fm2 <= 255 && ((fm2 + 1) / 2 + K) * (int)FG <= cap ? fm2 : fm;
 }
 
 // F[i] = fence of position i*FG (the first multi-way pass after the SORT tile).
@@ -379,7 +194,7 @@ __global__ __launch_bounds__(1024) void k_fence_merge(const FT* __restrict__ F, 
 }
 
 // Chunk index -> (group, chunk within the group), and the group's first chunk.
-// Chunk and bounds-slot indices are < 2^31 (merge_pass checks), so the
+// Chunk and bounds-slot indices are < 2^31 (plan_pass checks), so the
 // divisions are 32-bit.
 __device__ __forceinline__ void chunk_place(const Geo& geo, int64_t c, int64_t& g, int64_t& t) {
     if (c < geo.nfull * geo.kf) {
@@ -390,8 +205,6 @@ __device__ __forceinline__ void chunk_place(const Geo& geo, int64_t c, int64_t& 
         t = c - geo.nfull * geo.kf;
     }
 }
-
-constexpr int SCAN_NT = SCAN_NT_MAX;  // chunks per block of the fence-count scan
 
 // Inclusive scan of a u64 over the block (all its lanes; sw holds one entry
 // per wave), for packed fields.
@@ -831,15 +644,8 @@ __global__ void k_bounds(const KEY* __restrict__ src, const typename KTr<KEY>::F
 // reads its LS entries as a few wide scalar loads.
 // Validated so that no chunk can address memory outside its group's runs:
 // a bad chunk gets no rows and is left unwritten (the sort then fails its
-// checks).
-template <typename KEY, int LK>
-struct alignas(128) Desc {  // whole 128-byte lines: a chunk's entries never share a line with another's
-    int64_t gbase, out0;
-    int o[Shape<KEY, LK>::K + 1];           // chunk position of segment r; o[K] = chunk length
-    uint32_t off[Shape<KEY, LK>::NROWS];  // byte offset of the row's first key from the group base
-    uint32_t la[Shape<KEY, LK>::NROWS];   // real keys of the row (0..RW) | LDS slot of its first key << 16
-};
-
+// checks).  The struct itself, Desc, is in mergek_plan.h (plan_pass sizes it).
+//
 // DC chunks per one-wave workgroup (16; 4 for small sorts, which then still
 // spread over many waves), in two phases.  Lane = chunk: read its 2K
 // bounds (one contiguous row), check them and prefix the segment lengths and
@@ -906,10 +712,10 @@ __device__ __forceinline__ void desc_entry(Desc<KEY, LK>* d, const DescHdr<KEY, 
     d->la[j] = la;
 }
 
-// The capacity split (merge_pass): chunk (g, t), whose exact size exceeds CAP,
+// The capacity split (plan_pass): chunk (g, t), whose exact size exceeds CAP,
 // cut at its middle merged fence into two descriptors d[0], d[1] by the 64
 // lanes of one wave.  Each half holds at most ceil(fm / 2) + K fences' worth
-// of keys <= CAP (merge_pass bounds fm so).  Lane r < K finds run r's bound at
+// of keys <= CAP (plan_pass bounds fm so).  Lane r < K finds run r's bound at
 // the middle fence: its fences before the chunk start (the scanned counts)
 // plus those among the chunk's first fences, then the window search of
 // k_bounds; lanes 0 and 1 build the halves' headers.  hdr / seg / sm: LDS
@@ -969,7 +775,6 @@ __device__ __forceinline__ void split_chunk(const KEY* __restrict__ src, const t
 // holds the RAW block totals of the nbs fence-count blocks (nbs * K <=
 // PLAN_SCAN_MAX) and every workgroup scans them in LDS, in place of a
 // k_scan_totals launch (a few KB of L2 reads per workgroup).
-constexpr int PLAN_SCAN_MAX = 2048;
 template <typename KEY, int LK, int DC, bool PLAN>
 __global__ __launch_bounds__(DC_NT) void k_chunk_desc(const int64_t* __restrict__ bounds, Geo geo, int64_t nchunks,
                                                    Desc<KEY, LK>* __restrict__ desc, int* __restrict__ err,
@@ -1057,7 +862,7 @@ __global__ __launch_bounds__(DC_NT) void k_chunk_desc(const int64_t* __restrict_
             ok = ok && st[r] >= 0 && ln >= 0 && en[r] <= geo.run_len(g, r);
             tot += ln;
         }
-        // ovf (fm above the worst-case bound, see merge_pass): a chunk larger
+        // ovf (fm above the worst-case bound, see plan_pass): a chunk larger
         // than CAP keys gets an empty descriptor here and is listed in ovf for
         // k_split_desc
         const bool big = ok && tot > S::CAP;
@@ -1334,7 +1139,7 @@ void* scratch(int which, size_t bytes, hipStream_t s) {
 }
 
 // One error word per (device, stream): k_chunk_desc sets it when it rejects
-// a chunk's bounds (mergek_take_error reads and clears it).
+// a chunk's bounds (take_error reads and clears it).
 std::map<std::pair<int, hipStream_t>, int*> g_errw;
 int* error_word(hipStream_t s) {
     int dev = 0;
@@ -1351,230 +1156,183 @@ int* error_word(hipStream_t s) {
     return w;
 }
 
-int64_t chunks_of(const Geo& geo) {
-    const bool tail = (geo.nfull << (geo.lw + geo.lk)) < geo.n;
-    return geo.nfull * geo.kf + (tail ? geo.nchunks(geo.nfull) : 0);
-}
-
-// The fence merge levels of a u32 pass as one multi-way merge pass over the
-// fences themselves (u64 keys, depth 1) once at least FENCE_NEST_LEVELS of
-// them would run as global 2-way merge levels and the pass has at least
-// 2^MISORT_FENCE_NEST_MIN fences (env; 0 = never): one HBM sweep of the fence
-// array instead of one per level.  Measured (profiles/r05/plan/nest_ab.txt):
-// 2^30 u32 passes 3 and 4 (2^23 fences) -30 us each, +0.6 %; at 2^22 fences
-// (2^29 keys) the nested pass's ~600 chunks underfilled the chip: +5 us, so the
-// threshold was 2^23.  Round 6: with the nested pass's own planning in one
-// k_fence_rank launch, 2^21 measured 2^28 +0.5 %, 2^29 +0.6 %, 2^30 equal
-// (profiles/r06/plan/nest_ab.txt).
-constexpr int FENCE_NEST_LEVELS = 3;
+// A pass's device buffers: the plan's workspace parts as typed pointers.
+template <typename KEY, int LK>
+struct PassBufs {
+    typedef typename KTr<KEY>::F FT;
+    FT *F, *Fn, *M, *T;  // this pass's fences, the next pass's, the merged fences, the fence merge temp
+    int64_t* bounds;
+    int *cnt, *bsum, *ovf, *ew;  // ovf [count, chunks...] and dov (the listed chunks' halves): null without the split
+    Desc<KEY, LK>*desc, *dov;
+};
 
 template <typename KEY, int LK>
 hipError_t merge_pass(const KEY* src, KEY* dst, int64_t n, int lw, hipStream_t s, int phase, bool gather,
-                      int lk_next, LaunchHook* hook, bool ord_out, int depth = 0) {
-    typedef Shape<KEY, LK> S;
+                      int lk_next, LaunchHook* hook, bool ord_out, int depth = 0);
+
+// Step 1: the group's fences (gathered from src first if asked) into total
+// order, landing in M: one k_fence_rank launch (it also counts them), or the
+// first a levels in LDS and the other `left` as one nested pass or as fence
+// merge levels ping-ponging through T.
+template <typename KEY, int LK>
+hipError_t order_fences(const PassPlan& p, const PassBufs<KEY, LK>& b, const KEY* src, bool gather, hipStream_t s) {
     typedef typename KTr<KEY>::F FT;
-    // MISORT_PLAN_FUSE: 1 (default) = bounds inside k_chunk_desc below 4096
-    // chunks, 2 = at every size, 0 = never (profiles/r03/ab_plan: 2^24 u32 43.1
-    // -> 43.9 Gkeys/s; at 2^26, 9362 chunks, 65.2 -> 65.0)
-    // MISORT_PLAN_SCAN: 1 (default) = a fused descriptor kernel scans the
-    // fence-count block totals itself when they fit PLAN_SCAN_MAX, 0 = never
-    static const int plan_fuse = getenv("MISORT_PLAN_FUSE") ? atoi(getenv("MISORT_PLAN_FUSE")) : 1;
-    static const int plan_scan = getenv("MISORT_PLAN_SCAN") ? atoi(getenv("MISORT_PLAN_SCAN")) : 1;
-    Geo geo = make_geo<KEY>(n, lw, LK);
-    const bool fuse = plan_fuse == 2 || (plan_fuse == 1 && chunks_of(geo) < 4096);
-    // Capacity split (unfused passes): chunks cut every fm merged fences, fm
-    // above the worst-case bound by split_fm_add -- sized for a typical chunk,
-    // whose K window offsets nearly cancel -- and the rare chunk that exceeds
-    // CAP cut in two at its middle fence (k_chunk_desc cuts it, k_mergek's
-    // extra workgroups run the halves).  A half holds at most ceil(fm / 2) + K fences'
-    // worth of keys, so fm stays within 2 (CAP / FG - K) (and 8-bit counts).
-    const int fma = fuse ? 0 : split_fm_add<KEY, LK>();
-    if (fma > 0) geo = make_geo<KEY>(n, lw, LK, balance_fm<KEY, LK>(geo.fm + fma, ((int64_t)1 << (lw + LK)) >> FG_LOG2));
-    const bool split = fma > 0;
-    const bool tail = (geo.nfull << (lw + LK)) < n;
-    const int64_t nchunks = chunks_of(geo);
-    const int64_t nslots = geo.nfull * (geo.kf + 1) + (tail ? geo.nchunks(geo.nfull) + 1 : 0);
-    const int64_t nf = (n + FG - 1) >> FG_LOG2;
-    if (nchunks >= ((int64_t)1 << 31) || nslots >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-    // fence buffers 0 and 1 (kept across passes); per pass: merged fences,
-    // fence merge temp, bounds, fence counts and their block totals, descriptors
-    // chunks per fence-count block: SCAN_NT, or fewer (down to 32) while that
-    // leaves under 128 blocks -- a small sort's few blocks walked long slices
-    int cpb = SCAN_NT;
-    while (cpb > 32 && (nchunks + cpb - 1) / cpb < 128) cpb /= 2;
-    const int64_t nbk = (nchunks + cpb - 1) / cpb;
-    const size_t fb = ((size_t)nf * sizeof(FT) + 255) & ~(size_t)255;
-    const size_t bb = ((size_t)nslots * S::K * 8 + 255) & ~(size_t)255;
-    const size_t cb = ((size_t)nbk * cpb * S::K * 4 + 255) & ~(size_t)255;
-    const size_t sb = ((size_t)nbk * S::K * 4 + 255) & ~(size_t)255;
-    char* fbase = (char*)scratch(2 * depth, 2 * fb, s);
-    // descriptors: one per chunk, and with the split two per listed chunk
-    // (at most every chunk) plus the list
-    const size_t db = (size_t)nchunks * sizeof(Desc<KEY, LK>) * (split ? 3 : 1);
-    const size_t ob = split ? ((size_t)(nchunks + 1) * 4 + 255) & ~(size_t)255 : 0;
-    char* base = (char*)scratch(2 * depth + 1, 2 * fb + bb + cb + sb + db + ob + 256, s);
-    int* ew = error_word(s);
-    if (!base || !fbase || !ew) return hipErrorOutOfMemory;
-    FT* F = (FT*)(fbase + (phase & 1) * fb);
-    FT* Fn = (FT*)(fbase + ((phase & 1) ^ 1) * fb);
-    FT* M = (FT*)base;
-    FT* T = (FT*)(base + fb);
-    int64_t* bounds = (int64_t*)(base + 2 * fb);
-    int* cnt = (int*)(base + 2 * fb + bb);
-    int* bsum = (int*)(base + 2 * fb + bb + cb);
-    Desc<KEY, LK>* desc = (Desc<KEY, LK>*)(base + 2 * fb + bb + cb + sb);
-    Desc<KEY, LK>* dov = split ? desc + nchunks : nullptr;  // the halves of listed chunks
-    int* ovf = split ? (int*)(base + 2 * fb + bb + cb + sb + db) : nullptr;  // [count, chunks...]
-    if (gather) k_fence_gather<KEY><<<(unsigned)((nf + 255) / 256), 256, 0, s>>>(src, n, lw, LK, F);
-    const int wf_log2 = lw - FG_LOG2;  // fences per run = 2^wf_log2
-    // MISORT_FENCE_RANK_MAX: fused passes whose runs hold <= 2^this fences rank
-    // them and count them in one launch (k_fence_rank); 0 = never
-    static const int rank_max = getenv("MISORT_FENCE_RANK_MAX") ? atoi(getenv("MISORT_FENCE_RANK_MAX")) : 14;
-    const bool rank = fuse && wf_log2 <= rank_max;
-    if (rank) {
+    const int64_t nf = p.nf;
+    if (gather) k_fence_gather<KEY><<<(unsigned)((nf + 255) / 256), 256, 0, s>>>(src, p.geo.n, p.geo.lw, LK, b.F);
+    if (p.rank) {
         k_fence_rank<FT, LK><<<(unsigned)((nf + RANK_NT - 2) / (RANK_NT - 1)), RANK_NT, 0, s>>>(
-            F, M, geo, nf, wf_log2, cnt, bsum, nbk * S::K);
-    } else {
-        // the group's fences into total order, landing in M: the first a levels
-        // in LDS (sub-groups of 2^a runs, <= 64 KiB of fences), the other
-        // LK - a as fence merge levels (runs of >= 2^FL fences), ping-ponging
-        // through T
-        constexpr int FL = KTr<KEY>::FL_LDS;
-        const int a = wf_log2 >= FL ? 0 : (FL - wf_log2 < LK ? FL - wf_log2 : LK);
-        const FT* x = F;
-        int left = LK - a;
-        bool nest = false;
-        if constexpr (sizeof(KEY) == 4) {
-            static const int nest_min =
-                getenv("MISORT_FENCE_NEST_MIN") ? atoi(getenv("MISORT_FENCE_NEST_MIN")) : 21;
-            nest = depth == 0 && nest_min > 0 && left >= FENCE_NEST_LEVELS && nf >= ((int64_t)1 << nest_min) &&
-                   wf_log2 + a >= KTr<uint64_t>::LW_MIN && wf_log2 + a + left <= KTr<uint64_t>::LWK_MAX;
-        }
-        if (a > 0) {
-            FT* y = nest || (left & 1) ? T : M;
-            const size_t lds = ((size_t)1 << (wf_log2 + a)) * sizeof(FT);
-            const int64_t nb0 = (nf + ((int64_t)1 << (wf_log2 + a)) - 1) >> (wf_log2 + a);
-            // >= 512 blocks where the sub-groups are few (each loads its whole sub-group)
-            if (nb0 >= FENCE_MERGE_MIN_BLOCKS) {
-                k_fence_merge<FT><<<(unsigned)nb0, (unsigned)(((int64_t)1 << (wf_log2 + a)) / FIT), lds, s>>>(
-                    F, y, nf, wf_log2, a);
-            } else {
-                int split = 1;
-                while (split < 8 && nb0 * split < 512 && ((int64_t)1 << (wf_log2 + a)) / (split * 2) >= 1024)
-                    split *= 2;
-                k_fence_lds<FT><<<(unsigned)(nb0 * split), 1024, lds, s>>>(F, y, nf, wf_log2, a, split);
-            }
-            x = y;
-        }
-        if constexpr (sizeof(KEY) == 4) {
-            if (nest) {
-                // the fences' runs of 2^(wf_log2 + a) into M in one pass (it
-                // reads x -- F or T -- and leaves F to k_bounds)
-                const uint64_t* xf = (const uint64_t*)x;
-                const hipError_t e =
-                    left == 4 ? merge_pass<uint64_t, 4>(xf, (uint64_t*)M, nf, wf_log2 + a, s, 0, true, 0, nullptr, false, 1)
-                              : merge_pass<uint64_t, 3>(xf, (uint64_t*)M, nf, wf_log2 + a, s, 0, true, 0, nullptr, false, 1);
-                if (e != hipSuccess) return e;
-                left = 0;
-            }
-        }
-        for (int l = LK - left; l < LK; ++l, --left) {
-            FT* y = ((left - 1) & 1) ? T : M;
-            const hipError_t e = merge_level<FT>(x, y, nf, wf_log2 + l, s);
-            if (e != hipSuccess) return e;
-            x = y;
+            b.F, b.M, p.geo, nf, p.wf_log2, b.cnt, b.bsum, p.nbk << LK);
+        return hipSuccess;
+    }
+    const FT* x = b.F;
+    const int sg = p.wf_log2 + p.a;  // log2 fences of an LDS sub-group
+    if (p.a > 0) {
+        FT* y = p.nest || (p.left & 1) ? b.T : b.M;
+        const size_t lds = ((size_t)1 << sg) * sizeof(FT);
+        if (p.fmerge)
+            k_fence_merge<FT><<<(unsigned)p.nb0, (unsigned)(((int64_t)1 << sg) / FIT), lds, s>>>(b.F, y, nf, p.wf_log2, p.a);
+        else
+            k_fence_lds<FT><<<(unsigned)(p.nb0 * p.fsplit), 1024, lds, s>>>(b.F, y, nf, p.wf_log2, p.a, p.fsplit);
+        x = y;
+    }
+    if constexpr (sizeof(KEY) == 4) {
+        if (p.nest) {
+            // the fences' runs of 2^sg into M in one pass (it reads x -- F or T -- and leaves F to k_bounds)
+            const uint64_t* xf = (const uint64_t*)x;
+            return p.nest_lk == 4 ? merge_pass<uint64_t, 4>(xf, (uint64_t*)b.M, nf, sg, s, 0, true, 0, nullptr, false, 1)
+                                  : merge_pass<uint64_t, 3>(xf, (uint64_t*)b.M, nf, sg, s, 0, true, 0, nullptr, false, 1);
         }
     }
-    const int64_t nb = nbk;
-    // few blocks: per-lane slices; many: coalesced atomics (k_fence_counts)
-    // MISORT_FC_SLICES_MAX (tests): the block count from which the coalesced form counts
-    static const int64_t slices_max = getenv("MISORT_FC_SLICES_MAX") ? atoll(getenv("MISORT_FC_SLICES_MAX")) : 256;
-    if (rank) {
-    } else if (nb < slices_max) {
-        k_fence_counts<FT, true><<<(unsigned)nb, COUNT_NT, 0, s>>>(M, geo, nchunks, cpb, cnt, bsum, ovf);
-    } else {
-        k_fence_counts<FT, false><<<(unsigned)nb, FC_NT, 0, s>>>(M, geo, nchunks, cpb, cnt, bsum, ovf);
+    for (int left = p.left; left > 0; --left) {
+        FT* y = ((left - 1) & 1) ? b.T : b.M;
+        const hipError_t e = merge_level<FT>(x, y, nf, p.wf_log2 + LK - left, s);
+        if (e != hipSuccess) return e;
+        x = y;
     }
-    // planning kernel shapes by size (measured crossovers, profiles/r02/s3b-s3i):
-    // k_bounds' line probe from 2^17 searches, 16 descriptors per workgroup from 2^14 chunks
-    constexpr int64_t line_min = 1 << 17, dc16_min = 1 << 14;
-    const bool line = (nslots << LK) >= line_min;
-    const int nbs = !rank && fuse && plan_scan && nb * S::K <= PLAN_SCAN_MAX ? (int)nb : 0;
-    if (nbs == 0 && !rank) k_scan_totals<<<1, 64 * ((S::K + 1) / 2), 0, s>>>(bsum, nb, S::K);
-    if (!fuse)
-        k_bounds<KEY><<<(unsigned)(((nslots << LK) + 255) / 256), 256, 0, s>>>(src, F, M, cnt, bsum, cpb, geo,
-                                                                              nslots, bounds, line);
+    return hipSuccess;
+}
+
+// PER descriptors per workgroup; FUSED: the bounds computed inside (no k_bounds, no split).
+template <typename KEY, int LK, int PER, bool FUSED>
+void launch_chunk_desc(const PassPlan& p, const PassBufs<KEY, LK>& b, const KEY* src, hipStream_t s, hipEvent_t ta,
+                       hipEvent_t tb) {
+    typedef typename KTr<KEY>::F FT;
+    launch_timed(k_chunk_desc<KEY, LK, PER, FUSED>, dim3((unsigned)((p.nchunks + PER - 1) / PER)), dim3(DC_NT), 0, s, ta,
+                 tb, FUSED ? nullptr : (const int64_t*)b.bounds, p.geo, p.nchunks, b.desc, b.ew, FUSED ? src : nullptr,
+                 FUSED ? (const FT*)b.F : nullptr, FUSED ? (const FT*)b.M : nullptr, FUSED ? (const int*)b.cnt : nullptr,
+                 FUSED ? (const int*)b.bsum : nullptr, FUSED ? p.cpb : 0, FUSED && p.line, FUSED ? p.nbs : 0,
+                 FUSED ? nullptr : b.ovf, (Desc<KEY, LK>*)nullptr);
+}
+
+// Step 2: the merged fences into chunks: per-chunk fence counts and their scan
+// (unless k_fence_rank wrote them), the chunk bounds, the descriptors.
+template <typename KEY, int LK>
+void plan_chunks(const PassPlan& p, const PassBufs<KEY, LK>& b, const KEY* src, hipStream_t s, LaunchHook* hook) {
+    typedef typename KTr<KEY>::F FT;
+    constexpr int K = 1 << LK;
+    if (p.rank) {
+    } else if (p.slices) {
+        k_fence_counts<FT, true><<<(unsigned)p.nbk, COUNT_NT, 0, s>>>(b.M, p.geo, p.nchunks, p.cpb, b.cnt, b.bsum, b.ovf);
+    } else {
+        k_fence_counts<FT, false><<<(unsigned)p.nbk, FC_NT, 0, s>>>(b.M, p.geo, p.nchunks, p.cpb, b.cnt, b.bsum, b.ovf);
+    }
+    if (p.nbs == 0 && !p.rank) k_scan_totals<<<1, 64 * ((K + 1) / 2), 0, s>>>(b.bsum, p.nbk, K);
+    if (!p.fuse)
+        k_bounds<KEY><<<(unsigned)(((p.nslots << LK) + 255) / 256), 256, 0, s>>>(src, b.F, b.M, b.cnt, b.bsum, p.cpb, p.geo,
+                                                                                p.nslots, b.bounds, p.line);
     // the launch before k_mergek: a binding hook's tick (its end starts k_mergek's record)
     hipEvent_t ta = nullptr, tb = nullptr;
     if (hook && hook->binds()) (void)hook->bind(-1, -1, 0.0, &ta, &tb);
-    hipEvent_t da = ta, dbe = tb;
-    const dim3 g16((unsigned)((nchunks + 15) / 16)), g4((unsigned)((nchunks + 3) / 4));
-    const int* P0 = cnt;
-    const FT* F0 = F;
-    const FT* M0 = M;
-    if (fuse) {
-        if (nchunks >= dc16_min)
-            launch_timed(k_chunk_desc<KEY, LK, 16, true>, g16, dim3(DC_NT), 0, s, da, dbe, (const int64_t*)nullptr, geo,
-                         nchunks, desc, ew, src, F0, M0, P0, (const int*)bsum, cpb, line, nbs, (int*)nullptr,
-                         (Desc<KEY, LK>*)nullptr);
-        else
-            launch_timed(k_chunk_desc<KEY, LK, 4, true>, g4, dim3(DC_NT), 0, s, da, dbe, (const int64_t*)nullptr, geo,
-                         nchunks, desc, ew, src, F0, M0, P0, (const int*)bsum, cpb, line, nbs, (int*)nullptr,
-                         (Desc<KEY, LK>*)nullptr);
-    } else {
-        if (nchunks >= dc16_min)
-            launch_timed(k_chunk_desc<KEY, LK, 16, false>, g16, dim3(DC_NT), 0, s, da, dbe, (const int64_t*)bounds,
-                         geo, nchunks, desc, ew, (const KEY*)nullptr, (const FT*)nullptr, (const FT*)nullptr,
-                         (const int*)nullptr, (const int*)nullptr, 0, false, 0, ovf, (Desc<KEY, LK>*)nullptr);
-        else
-            launch_timed(k_chunk_desc<KEY, LK, 4, false>, g4, dim3(DC_NT), 0, s, da, dbe, (const int64_t*)bounds, geo,
-                         nchunks, desc, ew, (const KEY*)nullptr, (const FT*)nullptr, (const FT*)nullptr,
-                         (const int*)nullptr, (const int*)nullptr, 0, false, 0, ovf, (Desc<KEY, LK>*)nullptr);
-    }
-    // the listed chunks' halves (k_mergek's extra workgroups merge them)
-    if (split)
-        k_split_desc<KEY, LK><<<SPLIT_WG, 64, 0, s>>>(src, F0, M0, P0, (const int*)bsum, cpb, geo,
-                                                      (const int64_t*)bounds, ovf, dov, ew, line);
+    if (p.fuse && p.dc == 16) launch_chunk_desc<KEY, LK, 16, true>(p, b, src, s, ta, tb);
+    else if (p.fuse) launch_chunk_desc<KEY, LK, 4, true>(p, b, src, s, ta, tb);
+    else if (p.dc == 16) launch_chunk_desc<KEY, LK, 16, false>(p, b, src, s, ta, tb);
+    else launch_chunk_desc<KEY, LK, 4, false>(p, b, src, s, ta, tb);
+    // the listed chunks' halves (k_mergek's extra workgroups merge them).  (ADVICE,
+    // low: launched after the tick, so k_mergek's record includes it; kept as is.)
+    if (p.split)
+        k_split_desc<KEY, LK><<<SPLIT_WG, 64, 0, s>>>(src, (const FT*)b.F, (const FT*)b.M, (const int*)b.cnt,
+                                                      (const int*)b.bsum, p.cpb, p.geo, (const int64_t*)b.bounds, b.ovf,
+                                                      b.dov, b.ew, p.line);
+}
+
+// Step 3: k_mergek, one workgroup per chunk, and MISORT_MK_PROBE's launches.
+template <typename KEY, int LK>
+hipError_t launch_mergek(const PassPlan& p, const PassBufs<KEY, LK>& b, const KEY* src, KEY* dst, int lk_next,
+                         bool ord_out, int depth, hipStream_t s, LaunchHook* hook) {
+    typedef typename KTr<KEY>::F FT;
+    constexpr int NT = Shape<KEY, LK>::NT;
     // the capacity split: ovf_wg more workgroups walk the cut chunks' halves
-    const unsigned grid = (unsigned)nchunks + (split ? ovf_wg<KEY, LK>() : 0);
-    const uint32_t np = (uint32_t)nchunks;
-    const Desc<KEY, LK>* dv = dov;
-    const int* ov = ovf;
+    // (ADVICE, low: ovf_wg assumes 256 CUs; kept as is)
+    const dim3 grid((unsigned)p.nchunks + (p.split ? ovf_wg<KEY, LK>() : 0));
+    const uint32_t np = (uint32_t)p.nchunks;
+    const Desc<KEY, LK>*desc = b.desc, *dv = b.dov;
+    const int* ov = b.ovf;
     // a binding hook: the launch carries its own events and ends the pass's
     // record; else marker events around it (nested in the pass's)
-    const double kb = 2.0 * (double)n * sizeof(KEY);
+    const double kb = 2.0 * (double)p.geo.n * sizeof(KEY);
     hipEvent_t ea = nullptr, eb = nullptr;
     const bool bound = hook && hook->binds();
     if (bound) (void)hook->bind(KIND_RUNSK_KERNEL, KIND_RUNSK, kb, &ea, &eb);
     else if (hook) hook->before(KIND_RUNSK_KERNEL, kb, s);
     if (lk_next > 0) {
-        launch_timed(k_mergek<KEY, LK, true>, dim3(grid), dim3(S::NT), 0, s, ea, eb, src, dst,
-                     (const Desc<KEY, LK>*)desc, Fn, lw + LK, lk_next, np, dv, ov);
+        launch_timed(k_mergek<KEY, LK, true>, grid, dim3(NT), 0, s, ea, eb, src, dst, desc, b.Fn, p.geo.lw + LK, lk_next,
+                     np, dv, ov);
     } else if (ord_out) {
         if constexpr (sizeof(KEY) == 8)
-            launch_timed(k_mergek<KEY, LK, false, 0, true>, dim3(grid), dim3(S::NT), 0, s, ea, eb, src, dst,
-                         (const Desc<KEY, LK>*)desc, (FT*)nullptr, 0, 0, np, dv, ov);
+            launch_timed(k_mergek<KEY, LK, false, 0, true>, grid, dim3(NT), 0, s, ea, eb, src, dst, desc, (FT*)nullptr, 0,
+                         0, np, dv, ov);
     } else {
-        launch_timed(k_mergek<KEY, LK, false>, dim3(grid), dim3(S::NT), 0, s, ea, eb, src, dst,
-                     (const Desc<KEY, LK>*)desc, (FT*)nullptr, 0, 0, np, dv, ov);
+        launch_timed(k_mergek<KEY, LK, false>, grid, dim3(NT), 0, s, ea, eb, src, dst, desc, (FT*)nullptr, 0, 0, np, dv, ov);
     }
     if (hook && !bound) hook->after(KIND_RUNSK_KERNEL, s);
-    static const bool probe = getenv("MISORT_MK_PROBE") && atoi(getenv("MISORT_MK_PROBE")) != 0;
-    if (probe && depth == 0) {
+    if (mergek_knobs().probe && depth == 0) {
         // same chunks, outputs to a scratch buffer (the sort is untouched)
         static KEY* junk = nullptr;
         static size_t junk_n = 0;
-        if (junk_n < (size_t)n) {
+        if (junk_n < (size_t)p.geo.n) {
             if (junk) (void)hipFree(junk);
             junk = nullptr;
-            if (hipMalloc(&junk, (size_t)n * sizeof(KEY)) != hipSuccess) return hipErrorOutOfMemory;
-            junk_n = (size_t)n;
+            if (hipMalloc(&junk, (size_t)p.geo.n * sizeof(KEY)) != hipSuccess) return hipErrorOutOfMemory;
+            junk_n = (size_t)p.geo.n;
         }
-        k_mergek<KEY, LK, false, 1><<<np, S::NT, 0, s>>>(src, junk, desc, nullptr, 0, 0, np, dv, ov);
-        k_mergek<KEY, LK, false, 2><<<np, S::NT, 0, s>>>(src, junk, desc, nullptr, 0, 0, np, dv, ov);
-        k_mergek<KEY, LK, false, 3><<<np, S::NT, 0, s>>>(src, junk, desc, nullptr, 0, 0, np, dv, ov);
+        k_mergek<KEY, LK, false, 1><<<np, NT, 0, s>>>(src, junk, desc, nullptr, 0, 0, np, dv, ov);
+        k_mergek<KEY, LK, false, 2><<<np, NT, 0, s>>>(src, junk, desc, nullptr, 0, 0, np, dv, ov);
+        k_mergek<KEY, LK, false, 3><<<np, NT, 0, s>>>(src, junk, desc, nullptr, 0, 0, np, dv, ov);
     }
     return hipGetLastError();
+}
+
+// One 2^LK-way pass: plan_pass (mergek_plan.h) decides everything -- chunk
+// geometry, kernel shapes, the workspace layout -- and the three steps above
+// launch it.  The fence set (the two fence buffers, kept across passes) and
+// the planning set come from scratch(); depth 1 = a pass nested in
+// order_fences, on its own two sets.
+template <typename KEY, int LK>
+hipError_t merge_pass(const KEY* src, KEY* dst, int64_t n, int lw, hipStream_t s, int phase, bool gather,
+                      int lk_next, LaunchHook* hook, bool ord_out, int depth) {
+    typedef typename KTr<KEY>::F FT;
+    PassPlan p;
+    if (!plan_pass<KEY, LK>(n, lw, depth, mergek_knobs(), p)) return hipErrorInvalidValue;
+    char* fbase = (char*)scratch(p.fence_set, p.fence_bytes, s);
+    char* base = (char*)scratch(p.plan_set, p.plan_bytes, s);
+    int* ew = error_word(s);
+    if (!base || !fbase || !ew) return hipErrorOutOfMemory;
+    PassBufs<KEY, LK> b;
+    b.F = (FT*)(fbase + (phase & 1) * p.fb);
+    b.Fn = (FT*)(fbase + ((phase & 1) ^ 1) * p.fb);
+    b.M = (FT*)(base + p.off[PassPlan::P_M]);
+    b.T = (FT*)(base + p.off[PassPlan::P_T]);
+    b.bounds = (int64_t*)(base + p.off[PassPlan::P_BOUNDS]);
+    b.cnt = (int*)(base + p.off[PassPlan::P_CNT]);
+    b.bsum = (int*)(base + p.off[PassPlan::P_BSUM]);
+    b.desc = (Desc<KEY, LK>*)(base + p.off[PassPlan::P_DESC]);
+    b.dov = p.split ? b.desc + p.nchunks : nullptr;
+    b.ovf = p.split ? (int*)(base + p.off[PassPlan::P_OVF]) : nullptr;
+    b.ew = ew;
+    const hipError_t e = order_fences<KEY, LK>(p, b, src, gather, s);
+    if (e != hipSuccess) return e;
+    plan_chunks<KEY, LK>(p, b, src, s, hook);
+    return launch_mergek<KEY, LK>(p, b, src, dst, lk_next, ord_out, depth, s, hook);
 }
 
 template <typename KEY>
@@ -1592,34 +1350,16 @@ hipError_t merge_levelk_t(const KEY* src, KEY* dst, int64_t n, int lw, int lk, h
     return merge_pass<KEY, 4>(src, dst, n, lw, s, phase, gather, lk_next, hook, ord_out);
 }
 
-}  // namespace
-
-int64_t MISORT_RUNSK_FN(mergek_chunks)(int64_t n, int lw, int lk, int key_bytes) {
-    return key_bytes == 8 ? chunks_of(make_geo<uint64_t>(n, lw, lk)) : chunks_of(make_geo<uint32_t>(n, lw, lk));
-}
-
-// phase: which of the two fence buffers holds this pass's input fences
-// (gather: build them from src first); lk_next > 0: write the next multi-way
-// pass's fences (runs of 2^(lw+lk) in groups of 2^lk_next) into the other
-// buffer.
-hipError_t MISORT_RUNSK_FN(merge_levelk)(const uint32_t* src, uint32_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
-                        bool gather, int lk_next, LaunchHook* hook) {
-    return merge_levelk_t<uint32_t>(src, dst, n, lw, lk, s, phase, gather, lk_next, hook);
-}
-hipError_t MISORT_RUNSK_FN(merge_levelk)(const uint64_t* src, uint64_t* dst, int64_t n, int lw, int lk, hipStream_t s, int phase,
-                        bool gather, int lk_next, LaunchHook* hook, bool ord_out) {
-    return merge_levelk_t<uint64_t>(src, dst, n, lw, lk, s, phase, gather, lk_next, hook, ord_out);
-}
-void* MISORT_RUNSK_FN(mergek_fence_buffer)(int64_t n, int key_bytes, int phase, hipStream_t s) {
-    // the sizes merge_pass computes, so the buffer never moves between the two
-    const int64_t nf = (n + FG - 1) >> FG_LOG2;
-    const size_t fb = ((size_t)nf * (key_bytes == 8 ? sizeof(u128) : sizeof(uint64_t)) + 255) & ~(size_t)255;
+// The SORT pass's fence buffer: phase `phase` of the fence set merge_pass uses
+// (the same fence_buffer_bytes, so the buffer never moves between the two).
+void* fence_buffer(int64_t n, int key_bytes, int phase, hipStream_t s) {
+    const size_t fb = fence_buffer_bytes(n, key_bytes == 8 ? sizeof(u128) : sizeof(uint64_t));
     char* fbase = (char*)scratch(0, 2 * fb, s);
     return fbase ? fbase + (phase & 1) * fb : nullptr;
 }
 // 1 if a merge pass on stream s rejected a chunk since the last call (the
 // stream is synchronised), else 0; negative on a HIP error.
-int MISORT_RUNSK_FN(mergek_take_error)(hipStream_t s) {
+int take_error(hipStream_t s) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
     int* w = nullptr;
@@ -1639,7 +1379,7 @@ int MISORT_RUNSK_FN(mergek_take_error)(hipStream_t s) {
 
 // Frees the fence and planning scratch kept for stream s on the current
 // device (misort_destroy, for the context's own stream).
-void MISORT_RUNSK_FN(mergek_release)(hipStream_t s) {
+void release(hipStream_t s) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return;
     std::lock_guard<std::mutex> g(g_mu);
@@ -1659,7 +1399,22 @@ void MISORT_RUNSK_FN(mergek_release)(hipStream_t s) {
         m.erase(it);
     }
 }
-#ifndef MISORT_RUNSK_SECOND
+
+}  // namespace
+
+// This build's handle (kernels.h); runsk_fg6.hip names its own.
+#ifndef MISORT_RUNSK_BUILD
+#define MISORT_RUNSK_BUILD mergek_build_default
+#define MISORT_RUNSK_FIRST 1
+#endif
+const MergekBuild& MISORT_RUNSK_BUILD() {
+    static const MergekBuild b = {FG_LOG2,      merge_levelk_t<uint32_t>, merge_levelk_t<uint64_t>,
+                                  fence_buffer, take_error,               release};
+    return b;
+}
+#ifdef MISORT_RUNSK_FIRST
+const MergekBuild& mergek_build_fg6();
+const MergekBuild& mergek_build(int fence_log2) { return fence_log2 == 6 ? mergek_build_fg6() : mergek_build_default(); }
 int merge_levelk_lw_min(int key_bytes) { return key_bytes == 8 ? KTr<uint64_t>::LW_MIN : KTr<uint32_t>::LW_MIN; }
 int merge_levelk_lwk_max(int key_bytes) { return key_bytes == 8 ? KTr<uint64_t>::LWK_MAX : KTr<uint32_t>::LWK_MAX; }
 #endif

@@ -3,6 +3,5 @@
 // so the fence slack K * FG halves) for twice the fences to plan with.  The
 // planner picks this build for large sorts (mergek_fence_log2, kernels.hip).
 #define MISORT_RUNSK_FGL 6
-#define MISORT_RUNSK_FN(x) x##_fg6
-#define MISORT_RUNSK_SECOND 1
+#define MISORT_RUNSK_BUILD mergek_build_fg6
 #include "runsk.hip"

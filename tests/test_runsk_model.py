@@ -1,27 +1,57 @@
 """numpy model of the K-way merge pass's chunking (runsk.hip), CPU only.
 
-Mirrors the kernels' constants and rules: fences every FG keys of each run,
-packed (key, run, position/FG) so that u64 order is the total order; the
-group's fences merged; every FM-th one starts a chunk whose start in each run
-is that run's count of keys before the fence; chunks are then merged
-independently.  Checks the properties the kernels rely on: chunks tile each
-group exactly, no chunk exceeds CAP keys nor the load rows (RW keys of one
-segment, NROWS per chunk), every chunk's keys precede the next chunk's, and
-the chunk/slot indexing (chunks per full group = ceil(fences / FM)) matches
-the bounds layout.  K = 2^lk, lk = 1..4."""
+The kernels' constants and the pass plan come from the library's own host code
+(csrc/mergek_plan.h), printed by lib/mergek_plan_dump (built by the default
+make target): nothing here is a literal copy.  The rules modelled: fences every
+FG keys of each run, packed (key, run, position/FG) so that u64 order is the
+total order; the group's fences merged; every fm-th one starts a chunk whose
+start in each run is that run's count of keys before the fence; chunks are
+then merged independently.  Checks the properties the kernels rely on: chunks
+tile each group exactly, no chunk exceeds CAP keys nor the load rows (RW keys
+of one segment, NROWS per chunk), every chunk's keys precede the next chunk's,
+and the chunk/slot indexing (chunks per full group = ceil(fences / fm)) matches
+the bounds layout -- with the worst-case fm, and with the raised fm of the
+capacity split, where a chunk over CAP is cut at its middle fence.  The plan's
+workspace layout and knob rules are checked from the dump alone
+(test_pass_layout).  K = 2^lk, lk = 1..4."""
+import functools
+import json
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
-FG_LOG2, CAP = 7, 8192
-NT, IT = 512, 18  # k_mergek lanes and keys per lane
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DUMP = os.path.join(ROOT, "parallel-computing-mpi_amd", "lib", "mergek_plan_dump")
+ASAN_DUMP = os.path.join(ROOT, "build", "asan", "mergek_plan_dump")
+
+
+def run_dump(args, knobs=None, exe=DUMP):
+    """The dump program's JSON lines for `args`; knobs = the MISORT_* settings it
+    sees (this process's own are not passed on; the rest of the environment is)."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MISORT_")}
+    env.update(knobs or {})
+    r = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, env=env, timeout=60)
+    assert r.returncode == 0 and r.stderr == "", (args, knobs, r.returncode, r.stderr[-2000:])
+    return [json.loads(line) for line in r.stdout.splitlines()]
+
+
+@functools.lru_cache(maxsize=None)
+def shape(lk, key_bytes=4, fgl=7):
+    """Shape<KEY, lk> and KTr<KEY> of the build with 2^fgl-key fences."""
+    return run_dump([key_bytes, lk, fgl])[0]
+
+
+def plans(ns, lw, lk, key_bytes=4, fgl=7, depth=0, knobs=None, exe=DUMP):
+    """plan_pass<KEY, lk>(n, lw, depth) for every n of ns."""
+    out = run_dump([",".join(map(str, ns)), lw, lk, key_bytes, fgl, depth], knobs, exe)
+    assert len(out) == len(ns) and all(p["ok"] for p in out)
+    return out
+
+
+FG_LOG2 = shape(1)["FG_LOG2"]  # the model runs the default build (u32 keys)
 FG = 1 << FG_LOG2
-
-
-def shape(lk):
-    """(K, FM, RW, NROWS) of runsk.hip's Shape<lk>."""
-    K = 1 << lk
-    rw = 64 if lk == 4 else 128 if lk == 3 else 256
-    return K, CAP // FG - K, rw, IT * NT // rw
 
 
 def fences(x, lw, lk, n):
@@ -32,17 +62,18 @@ def fences(x, lw, lk, n):
             | j.astype(np.uint64))
 
 
-def chunk_bounds(x, lw, lk, g, F):
-    """Start of every chunk of group g in each run (+ the end slot), as k_bounds."""
-    K, FM, _, _ = shape(lk)
+def chunk_bounds(x, lw, lk, g, F, fm):
+    """Start of every chunk of group g in each run (+ the end slot), as k_bounds;
+    and bound_at(i): the same for the group's i-th merged fence (k_split_desc)."""
+    K = 1 << lk
     n, W = x.size, 1 << lw
     base = g << (lw + lk)
     lens = [max(0, min(W, n - base - r * W)) for r in range(K)]
     f0, f1 = base >> FG_LOG2, (min(n, base + K * W) + FG - 1) >> FG_LOG2
     M = np.sort(F[f0:f1])
-    out = []
-    for t in range(0, (f1 - f0 + FM - 1) // FM):
-        f = int(M[t * FM])
+
+    def bound_at(i):
+        f = int(M[i])
         v, r0, j0 = f >> 32, (f >> (32 - lk)) & (K - 1), f & ((1 << (32 - lk)) - 1)
         st = []
         for r in range(K):
@@ -60,9 +91,11 @@ def chunk_bounds(x, lw, lk, g, F):
             lo = int(np.searchsorted(fr, np.uint64(f), side="left"))
             got = 0 if lo == 0 else refine(run, fr, lo, lens[r], v, r < r0)
             assert got == want
-        out.append(st)
+        return st
+
+    out = [bound_at(t * fm) for t in range(0, (f1 - f0 + fm - 1) // fm)]
     out.append(lens)
-    return out, lens
+    return out, lens, bound_at, f1 - f0
 
 
 def refine(run, fr, lo, ln, v, le):
@@ -107,40 +140,68 @@ def refine(run, fr, lo, ln, v, le):
     return lo_b
 
 
-@pytest.mark.parametrize("lk", [1, 2, 3, 4])
-@pytest.mark.parametrize("lw", [15, 16])
-@pytest.mark.parametrize("n_groups,tail", [(2, 0), (1, 3 * (1 << 15) + 5), (1, 777), (0, (1 << 15) * 2 + 1)])
-@pytest.mark.parametrize("kind", ["uniform", "dup", "equal", "interleaved"])
-def test_chunks_tile_and_bound(lk, lw, n_groups, tail, kind):
-    K, FM, RW, NROWS = shape(lk)
-    W = 1 << lw
-    n = n_groups * K * W + tail
-    rng = np.random.default_rng(lw + n)
+def make_keys(kind, n, lw, lk, seed, fm=0):
+    K, W = 1 << lk, 1 << lw
+    rng = np.random.default_rng(seed)
     if kind == "uniform":
         x = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
     elif kind == "dup":
         x = rng.integers(0, 7, n).astype(np.uint32)
     elif kind == "equal":
         x = np.full(n, 0xFFFFFFFF, np.uint32)
-    else:
+    elif kind == "interleaved":
         x = (np.arange(n) % K * 1000 + np.arange(n) // K).astype(np.uint32)
+    else:
+        # "clumped" (for chunks cut every fm fences): after a prefix of zeros, every
+        # run repeats a period of c + 1 fences, c = ceil(fm / K) -- one key 2m + 1,
+        # then (c + 1) FG - 1 keys 2m + 2 holding c fences.  The prefixes hold
+        # fm - K fences in all, so the group's chunk 1 starts at run 0's first
+        # fence of the first clump and takes nearly that whole clump from every
+        # run: its window offsets add up instead of cancelling, and it exceeds CAP.
+        c, i = -(-fm // K), np.arange(n)
+        r, pos = (i >> lw) & (K - 1), i & (W - 1)
+        q = pos - ((fm - K) // K + (r < (fm - K) % K)) * FG
+        per = (c + 1) * FG
+        x = np.where(q < 0, 0, 1 + 2 * (q // per) + (q % per != 0)).astype(np.uint32)
     for s in range(0, n, W):
         x[s:s + W].sort()
+    return x
+
+
+def check_groups(x, lw, lk, fm, groups, split):
+    """The chunking invariants on the given groups of x, cut every fm merged
+    fences; split: a chunk over CAP is cut at its middle merged fence into two
+    (k_chunk_desc lists it, k_split_desc cuts it) and each half must fit.
+    Returns the number of chunks cut."""
+    S = shape(lk)
+    K, CAP, RW, NROWS = S["K"], S["CAP"], S["RW"], S["NROWS"]
+    n, W = x.size, 1 << lw
     F = fences(x, lw, lk, n)
-    ngroups = (n + K * W - 1) // (K * W)
-    kf = ((K * W >> FG_LOG2) + FM - 1) // FM
-    for g in range(ngroups):
-        bounds, lens = chunk_bounds(x, lw, lk, g, F)
+    kf = ((K * W >> FG_LOG2) + fm - 1) // fm
+    ncut = 0
+    for g in groups:
+        bounds, lens, bound_at, nfg = chunk_bounds(x, lw, lk, g, F, fm)
         if (g + 1) * K * W <= n:
             assert len(bounds) - 1 == kf
         base = g << (lw + lk)
         merged = []
         prev_max = None
         assert bounds[0] == [0] * K
-        for a, b in zip(bounds[:-1], bounds[1:]):
+        pieces = []
+        for t, (a, b) in enumerate(zip(bounds[:-1], bounds[1:])):
+            size = sum(b[r] - a[r] for r in range(K))
+            if split and size > CAP:
+                mid = min(fm, nfg - t * fm) // 2
+                assert mid > 0
+                m = bound_at(t * fm + mid)
+                pieces += [(a, m), (m, b)]
+                ncut += 1
+            else:
+                pieces.append((a, b))
+        for a, b in pieces:
             seg = [x[base + r * W + a[r]: base + r * W + b[r]] for r in range(K)]
             size = sum(s.size for s in seg)
-            assert all(b[r] >= a[r] for r in range(K)) and size <= CAP
+            assert all(0 <= a[r] <= b[r] <= lens[r] for r in range(K)) and size <= CAP
             # load rows: each row of RW keys inside one segment, NROWS per chunk
             assert sum(-(-s.size // RW) for s in seg) <= NROWS
             chunk = np.sort(np.concatenate(seg))
@@ -151,6 +212,140 @@ def test_chunks_tile_and_bound(lk, lw, n_groups, tail, kind):
             merged.append(chunk)
         want = np.sort(x[base: base + sum(lens)])
         np.testing.assert_array_equal(np.concatenate(merged), want)
+    return ncut
+
+
+@pytest.mark.parametrize("lk", [1, 2, 3, 4])
+@pytest.mark.parametrize("lw", [15, 16])
+@pytest.mark.parametrize("n_groups,tail", [(2, 0), (1, 3 * (1 << 15) + 5), (1, 777), (0, (1 << 15) * 2 + 1)])
+@pytest.mark.parametrize("kind", ["uniform", "dup", "equal", "interleaved"])
+def test_chunks_tile_and_bound(lk, lw, n_groups, tail, kind):
+    """The worst-case fm, (fm + K) * FG <= CAP: no chunk can exceed CAP.  It is
+    what the plan cuts these sizes at (fused passes have no capacity split)."""
+    S = shape(lk)
+    K, FM, W = S["K"], S["FM"], 1 << lw
+    assert (FM + K) * FG <= S["CAP"] < (FM + K + 1) * FG and S["NROWS"] == S["LS"] * S["NR"]
+    assert S["NT"] % S["RW"] == 0 and S["NR"] == S["NT"] // S["RW"] and S["CAP"] <= S["NT"] * S["IT"]
+    n = n_groups * K * W + tail
+    x = make_keys(kind, n, lw, lk, lw + n)
+    ngroups = (n + K * W - 1) // (K * W)
+    assert check_groups(x, lw, lk, FM, range(ngroups), split=False) == 0
+    p = plans([n], lw, lk)[0]
+    kf = ((K * W >> FG_LOG2) + FM - 1) // FM
+    assert (p["fuse"], p["split"], p["fm"], p["kf"], p["nfull"]) == (1, 0, FM, kf, n >> (lw + lk))
+
+
+@pytest.mark.parametrize("lk", [3, 4])
+@pytest.mark.parametrize("kind", ["uniform", "dup", "equal", "interleaved", "clumped"])
+def test_chunks_tile_and_bound_split(lk, kind):
+    """The shipped shape of a large pass: the smallest u32 size (runs of 2^14)
+    whose plan is unfused -- 4096 chunks at the worst-case fm -- cuts at the
+    plan's raised fm and splits the chunks that then exceed CAP.  The plan's
+    counts are checked on the whole size from the dump; the group invariants on
+    keys of 4 full groups plus the tail group (a group's chunking depends on fm
+    and the group alone)."""
+    lw = 14
+    S = shape(lk)
+    K, FM, W = S["K"], S["FM"], 1 << lw
+    gf = K * W >> FG_LOG2  # fences of a full group
+    tail = 3 * W + 5
+    nfull = -(-4096 // (-(-gf // FM)))
+    n = nfull * K * W + tail
+    small, p = plans([n - K * W, n], lw, lk)
+    assert small["fuse"] == 1 and (p["fuse"], p["split"], p["rank"]) == (0, 1, 0)
+    fm = p["fm"]
+    # above the worst case, halves still fit, 8-bit fence counts
+    assert FM < fm <= 255 and ((fm + 1) // 2 + K) * FG <= S["CAP"]
+    kf, tail_chunks = -(-gf // fm), -(-((tail + FG - 1) >> FG_LOG2) // fm)
+    assert (p["kf"], p["nfull"], p["tail"]) == (kf, nfull, 1)
+    assert p["nchunks"] == nfull * kf + tail_chunks
+    assert nfull * -(-gf // FM) + -(-((tail + FG - 1) >> FG_LOG2) // FM) >= 4096  # unfused: by the worst-case count
+    assert p["nslots"] == p["nchunks"] + nfull + 1
+    x = make_keys(kind, 4 * K * W + tail, lw, lk, lk, fm)
+    ncut = check_groups(x, lw, lk, fm, range(5), split=True)
+    if kind == "clumped":
+        assert ncut >= 4  # the split is exercised, not only allowed: chunk 1 of every full group
+
+
+PASS_NS = [lambda lw: (1 << lw) + 1, lambda lw: (1 << 20) + 77, lambda lw: (1 << 24) + 999,
+           lambda lw: (1 << 26) + 12345, lambda lw: 1 << 30]
+
+
+def layout_grid(key_bytes, fgl):
+    """(lk, lw, depth, ns) over lk = 1..4, the shortest, a middle and the longest
+    runs a pass takes, both depths and the five sizes."""
+    for lk in (1, 2, 3, 4):
+        S = shape(lk, key_bytes, fgl)
+        for lw in sorted({S["LW_MIN"], 18, S["LWK_MAX"] - lk}):
+            for depth in (0, 1):
+                yield lk, lw, depth, [f(lw) for f in PASS_NS]
+
+
+def check_layout(p, S, depth):
+    K, parts = S["K"], {q["name"]: q for q in p["parts"]}
+    assert [q["name"] for q in p["parts"]] == ["M", "T", "bounds", "cnt", "bsum", "desc", "ovf"]
+    end = 0
+    for q in p["parts"]:  # aligned, disjoint, in order
+        assert q["off"] % 256 == 0 and q["bytes"] % 256 == 0 and q["off"] >= end
+        end = q["off"] + q["bytes"]
+    assert end <= p["plan_bytes"]
+    need = {"M": p["nf"] * S["fence_bytes"], "T": p["nf"] * S["fence_bytes"], "bounds": p["nslots"] * K * 8,
+            "cnt": p["nbk"] * p["cpb"] * K * 4, "bsum": p["nbk"] * K * 4,
+            "desc": p["nchunks"] * S["desc_bytes"] * (3 if p["split"] else 1),
+            "ovf": (p["nchunks"] + 1) * 4 if p["split"] else 0}
+    for name, b in need.items():
+        assert parts[name]["bytes"] >= b, name
+    assert p["fb"] == p["fence_buffer_fb"] and p["fb"] % 256 == 0 and p["fb"] >= need["M"]
+    assert p["fence_bytes"] == 2 * p["fb"] and (p["fence_set"], p["plan_set"]) == (2 * depth, 2 * depth + 1)
+    # the counts the sizes stand on
+    ngroups = -(-p["n"] >> (p["lw"] + p["lk"]))
+    assert p["nf"] == -(-p["n"] >> S["FG_LOG2"]) and p["nslots"] == p["nchunks"] + ngroups
+    assert p["nbk"] * p["cpb"] >= p["nchunks"] > (p["nbk"] - 1) * p["cpb"] and p["cpb"] in (32, 64, 128, 256)
+    assert p["dc"] in (4, 16) and S["desc_bytes"] % 128 == 0
+    assert p["fm_worst"] == S["FM"] and (p["fm"] > S["FM"] if p["split"] else p["fm"] == S["FM"])
+    assert not (p["fuse"] and p["split"]) and not (p["rank"] and not p["fuse"]) and not (p["nest"] and p["rank"])
+    assert p["nest_lk"] == (p["left"] if p["nest"] else 0) and (not p["nest"] or p["nest_lk"] in (3, 4))
+
+
+@pytest.mark.parametrize("fgl", [7, 6])
+@pytest.mark.parametrize("key_bytes", [4, 8])
+def test_pass_layout(key_bytes, fgl):
+    """plan_pass's workspace parts are 256-byte aligned, disjoint, in order
+    inside the reported total and large enough for what the plan's counts say is
+    written there; the fence buffer is the one MergekBuild::fence_buffer sizes; and
+    the knob rules the GPU variants (test_gpu_runs.py) rely on hold."""
+    seen = set()
+    for lk, lw, depth, ns in layout_grid(key_bytes, fgl):
+        S = shape(lk, key_bytes, fgl)
+        for p in plans(ns, lw, lk, key_bytes, fgl, depth):
+            check_layout(p, S, depth)
+            assert not (p["nest"] and (depth == 1 or key_bytes == 8))
+            seen |= {k for k in ("fuse", "split", "rank", "nest", "line", "slices", "fmerge", "nbs") if p[k]}
+            seen |= {"unfused"} if not p["fuse"] else set()
+        if depth == 1:
+            continue
+        for knobs, rule in [({"MISORT_PLAN_FUSE": "0"}, lambda p: not p["fuse"] and not p["rank"]),
+                            ({"MISORT_PLAN_FUSE": "2"}, lambda p: p["fuse"] and not p["split"]),
+                            ({"MISORT_MK_FM_ADD": "0"}, lambda p: not p["split"] and p["fm"] == p["fm_worst"]),
+                            ({"MISORT_FENCE_NEST_MIN": "0"}, lambda p: not p["nest"]),
+                            ({"MISORT_FENCE_RANK_MAX": "0"}, lambda p: not p["rank"])]:
+            for p in plans(ns, lw, lk, key_bytes, fgl, depth, knobs):
+                check_layout(p, S, depth)
+                assert rule(p), (knobs, p)
+    # the grid reaches every shape the defaults have for this key type
+    want = {"fuse", "unfused", "rank", "line", "slices", "fmerge", "nbs"} | ({"split", "nest"} if key_bytes == 4 else set())
+    assert want <= seen, want - seen
+
+
+def test_plan_dump_clean_under_asan_ubsan():
+    """The same grid through the dump program built with ASan + UBSan (a
+    stand-alone executable, nothing preloaded for it): exit status 0, no report."""
+    assert os.path.exists(ASAN_DUMP), "sanitized dump missing: make -C parallel-computing-mpi_amd/csrc asan"
+    for key_bytes in (4, 8):
+        for fgl in (7, 6):
+            for lk, lw, depth, ns in layout_grid(key_bytes, fgl):
+                assert run_dump([key_bytes, lk, fgl], exe=ASAN_DUMP)[0] == shape(lk, key_bytes, fgl)
+                assert plans(ns, lw, lk, key_bytes, fgl, depth, exe=ASAN_DUMP) == plans(ns, lw, lk, key_bytes, fgl, depth)
 
 
 def fence_rank_model(F, nf, wf_log2, lk, fm, nt=256):
