@@ -5,6 +5,7 @@
 // levels.  Every sequence is followed by G words of MAX (sentinels), so the
 // chains need no end checks.
 #pragma once
+#include "corank_seed.h"
 #include "kernels.h"
 
 namespace misort {
@@ -63,51 +64,63 @@ __device__ __forceinline__ KEY lds_ld(uint32_t a) {
 // no i == lo test.  The probes then run on byte addresses of A (j = &A[i-1]; B's
 // probe at C - j), five VALU and two LDS reads per step instead of seven VALU,
 // an SALU or and two reads.
-template <typename KEY, int MAXR, bool ZW = false>
-__device__ __forceinline__ int co_rank(const KEY* s, int A0, int LA, int B0, int LB, int d, int maxr) {
+//
+// The search itself -- its seed, window, step schedule, clamps and failure test
+// -- is corank_seed.h (host and device; corank_seed_dump.cpp is its host model);
+// here are the key loads and the wave's vote.  L: the level's uniform bounds.
+// full (uniform, sticky over the levels of a chunk or tile): the wave runs the
+// full search; set when any of its lanes' seeded searches fails, so keys that
+// defeat the guess (sorted, reversed, runs of ties) cost a wave one short
+// search per chunk.  EQ: LA == LB by the shape (the guess is d / 2).
+template <typename KEY, int MAXR, int UL, bool EQ, typename Probe>
+__device__ __forceinline__ int co_rank_run(int x0, int LA, int LB, int d, int lo, int hi, const corank::Level& L,
+                                           bool& full, Probe&& ok) {
+    constexpr int KB = (int)sizeof(KEY);
+    constexpr int PH = corank::phase_full(KB), PHS = corank::phase_seed(KB);
     // first co-rank step: the largest power of two <= MAXR + PH (MAXR: a
     // compile-time bound on hi - lo, the steps must be powers of two for the
     // lifting search); steps above maxr + PH (uniform) are skipped
-    constexpr int PH = sizeof(KEY) == 4 ? 31 : 0;
-    constexpr int CO_STEP0 = 1 << (31 - __builtin_clz((unsigned)(MAXR + PH)));
+    constexpr int CO_STEP0 = corank::floor_pow2(MAXR + PH);
     static_assert(MAXR + PH <= 2 * CO_STEP0 - 1, "co-rank steps cover the range");
+    // the seeded search's: a pair holds <= 2 MAXR keys
+    constexpr int SEED_STEP0 = corank::seed_step0(2 * MAXR, PHS) < CO_STEP0 ? corank::seed_step0(2 * MAXR, PHS) : CO_STEP0;
+    const int lane = (int)__lane_id();
+    int x = 0;
+    bool run_full = true;
+    if constexpr (corank::seed_built(KB)) {
+        if (L.seeded && !full) {  // uniform
+            bool failed;
+            x = corank::seeded<SEED_STEP0, UL, EQ>(x0, LA, LB, d, lo, hi, PHS ? lane & PHS : 0, L, failed, ok);
+            full = __builtin_amdgcn_ballot_w64(failed) != 0;  // one ballot, a uniform branch
+            run_full = full;
+        }
+    }
+    if (run_full) x = corank::full<CO_STEP0, UL>(x0, lo, hi, PH ? lane & 31 : 0, L, ok);
+    return corank::split_of<UL>(x, x0, lo);
+}
+
+template <typename KEY, int MAXR, bool ZW = false, bool EQ = false>
+__device__ __forceinline__ int co_rank(const KEY* s, int A0, int LA, int B0, int LB, int d, const corank::Level& L,
+                                       bool& full) {
     const int lo = d - LB > 0 ? d - LB : 0;
     const int hi = d < LA ? d : LA;
     const KEY* a = s + A0 - 1;
     const KEY* b = s + B0 + d;
-    int base = lo - (PH ? (int)(__lane_id() & 31) : 0);
     if constexpr (ZW) {
-        constexpr int W = (int)sizeof(KEY), WL = W == 4 ? 2 : 3;
+        constexpr int WL = sizeof(KEY) == 4 ? 2 : 3;
         const int ab = (int)lds_addr<KEY>(a);
         const int C = ab + (int)lds_addr<KEY>(b);  // b[-i] at C - &a[i]
-        const int jlo = ab + (lo << WL), jhi = ab + (hi << WL);
-        int jb = ab + (base << WL);
-#pragma unroll
-        for (int step = CO_STEP0; step >= 1; step >>= 1) {
-            if (step > maxr + PH) continue;  // uniform
-            const int t = jb + (step << WL);
-            int j;
-            asm("v_med3_i32 %0, %1, %2, %3" : "=v"(j) : "v"(t), "v"(jlo), "v"(jhi));
-            const bool ok = lds_ld<KEY>((uint32_t)j) <= lds_ld<KEY>((uint32_t)(C - j));
-            jb = ok ? j : jb;
-        }
-        base = (jb - ab) >> WL;
-        return base > lo ? base : lo;
+        return co_rank_run<KEY, MAXR, WL, EQ>(ab, LA, LB, d, lo, hi, L, full, [&](int j) {
+            return lds_ld<KEY>((uint32_t)j) <= lds_ld<KEY>((uint32_t)(C - j));
+        });
     } else {
         // a probe at hi that holds makes hi the answer (later probes repeat
         // it); a step that ends below lo tests lo, which holds by definition
         // (the answer is >= lo) and moves base up to lo, within the steps
-        // left; with a common start (PH = 0) no step ends below lo
-#pragma unroll
-        for (int step = CO_STEP0; step >= 1; step >>= 1) {
-            if (step > maxr + PH) continue;  // uniform
-            const int t = base + step;
-            int i;  // clamp(t, lo, hi)
-            asm("v_med3_i32 %0, %1, %2, %3" : "=v"(i) : "v"(t), "v"(lo), "v"(hi));
-            const bool ok = (PH != 0 && i == lo) | (a[i] <= b[-i]);
-            base = ok ? i : base;
-        }
-        return base > lo ? base : lo;
+        // left; with a common start (no phase) no step ends below lo
+        constexpr bool PHASED = corank::phase_full((int)sizeof(KEY)) != 0;
+        return co_rank_run<KEY, MAXR, 0, EQ>(0, LA, LB, d, lo, hi, L, full,
+                                             [&](int i) { return (PHASED && i == lo) | (a[i] <= b[-i]); });
     }
 }
 
@@ -119,12 +132,12 @@ __device__ __forceinline__ int co_rank(const KEY* s, int A0, int LA, int B0, int
 // one LDS read per output (u32).  Ties may go either way: equal keys are
 // identical.  Past the end of both sequences a chain outputs MAX (their
 // sentinels).
-template <typename KEY, int IT, int MAXR, bool ZW = false>
-__device__ __forceinline__ void merge_chain(const KEY* s, int A0, int LA, int B0, int LB, int d, int maxr,
-                                            KEY (&r)[IT]) {
+template <typename KEY, int IT, int MAXR, bool ZW = false, bool EQ = false>
+__device__ __forceinline__ void merge_chain(const KEY* s, int A0, int LA, int B0, int LB, int d,
+                                            const corank::Level& L, bool& full, KEY (&r)[IT]) {
     const int tot = LA + LB;
     const int dc = d < tot ? d : tot;  // lanes past the end: MAX outputs, in-bounds reads
-    const int ia = co_rank<KEY, MAXR, ZW>(s, A0, LA, B0, LB, dc, maxr);
+    const int ia = co_rank<KEY, MAXR, ZW, EQ>(s, A0, LA, B0, LB, dc, L, full);
     // byte addresses of the two heads (LDS pointers are 32-bit)
     uint32_t px = lds_addr<KEY>(s + A0 + ia), py = lds_addr<KEY>(s + B0 + dc - ia);
     KEY h = lds_ld<KEY>(px), g = lds_ld<KEY>(py);
@@ -197,13 +210,13 @@ __device__ __forceinline__ kvec2<KEY> lds_ld2(uint32_t a) {
 // outputs (u32) -- the one-key chain spends six VALU and an LDS read per
 // output.  A side gives at most IT keys, so the G >= IT sentinels after each
 // sequence cover every read.
-template <typename KEY, int IT, int MAXR, bool ZW = false>
-__device__ __forceinline__ void merge_chain_blk(const KEY* s, int A0, int LA, int B0, int LB, int d, int maxr,
-                                                KEY (&r)[IT]) {
+template <typename KEY, int IT, int MAXR, bool ZW = false, bool EQ = false>
+__device__ __forceinline__ void merge_chain_blk(const KEY* s, int A0, int LA, int B0, int LB, int d,
+                                                const corank::Level& L, bool& full, KEY (&r)[IT]) {
     static_assert(IT % 2 == 0, "two outputs per step");
     const int tot = LA + LB;
     const int dc = d < tot ? d : tot;
-    const int ia = co_rank<KEY, MAXR, ZW>(s, A0, LA, B0, LB, dc, maxr);
+    const int ia = co_rank<KEY, MAXR, ZW, EQ>(s, A0, LA, B0, LB, dc, L, full);
     constexpr uint32_t B2 = 2 * sizeof(KEY);
     const uint32_t pa = lds_addr<KEY>(s + A0 + ia), pb = lds_addr<KEY>(s + B0 + dc - ia);
     const kvec2<KEY> a = lds_ld2<KEY>(pa), b = lds_ld2<KEY>(pb);
@@ -263,15 +276,17 @@ constexpr int uni_in_stride(int lv) { return lv == 1 ? S::RUN + S::GS : uni_stri
 // sentinels) and holds lp[p] keys; maxr bounds its co-rank range (uniform).
 template <typename S>
 __device__ __forceinline__ void level_geometry(const int* ln, int P, int (&qp)[S::K / 2], int (&lp)[S::K / 2],
-                                               int& maxr) {
+                                               int& maxr, int& maxt) {
     int qa = 0;
     maxr = 0;
+    maxt = 0;
 #pragma unroll
     for (int p = 0; p < S::K / 2; ++p) {
         if (p >= P) break;
         const int mr = ln[2 * p] < ln[2 * p + 1] ? ln[2 * p] : ln[2 * p + 1];
         maxr = mr > maxr ? mr : maxr;
         lp[p] = ln[2 * p] + ln[2 * p + 1];
+        maxt = lp[p] > maxt ? lp[p] : maxt;
         qp[p] = qa;
         qa = (qa + lp[p] + S::G + S::QA - 1) / S::QA * S::QA;
     }
@@ -306,6 +321,8 @@ __device__ __forceinline__ void lds_merge_levels(KEY* s, int (&st)[S::K], int (&
                                                  int LAST) {
     constexpr int K = S::K, LK = S::LKS, NT = S::NT, IT = S::IT, G = S::G, CH = S::CH;
     constexpr bool ZW = shape_zw<S>::v;
+    constexpr bool EQ = shape_uni<S>::v;  // a uniform shape's pairs: LA == LB
+    bool full = false;  // the wave's sticky fallback to the full co-rank search (co_rank_run)
     static_assert(CH == 0 || CH == 1, "one- or two-key chains");
     // a two-key chain reads at most IT keys past a sequence (the one-key chain
     // IT + 1), so the G-th word after it is free for the next sequence's zero word
@@ -320,12 +337,14 @@ __device__ __forceinline__ void lds_merge_levels(KEY* s, int (&st)[S::K], int (&
         // pair p's output: [qp[p], qp[p] + lp[p]), then G sentinels; the next
         // pair starts at the first lane boundary past them
         int qp[K / 2], lp[K / 2];
-        int maxr;  // the longest co-rank range of the level's pairs (uniform)
-        level_geometry<S>(ln, P, qp, lp, maxr);
+        int maxr, maxt;  // the longest co-rank range and the largest pair of the level (uniform)
+        level_geometry<S>(ln, P, qp, lp, maxr, maxt);
         // uniform: the co-rank searches skip their long steps by scalar
-        // branches (a maxr the compiler left in a VGPR costs every step a
+        // branches (a bound the compiler left in a VGPR costs every step a
         // compare and an exec-mask save / restore)
         maxr = __builtin_amdgcn_readfirstlane(maxr);
+        maxt = __builtin_amdgcn_readfirstlane(maxt);
+        const corank::Level L = corank::level(maxr, maxt, (int)sizeof(KEY));  // scalar work
         // the lane's pair: the last one starting at or before pos
         int A0 = st[0], LA = ln[0], B0 = st[1], LB = ln[1], Q = 0, LP = lp[0];
         if (P > 1) {
@@ -359,13 +378,13 @@ __device__ __forceinline__ void lds_merge_levels(KEY* s, int (&st)[S::K], int (&
             for (int j = 0; j < IT; ++j) r[j] = s[pos + j < LAST ? pos + j : LAST];
             if (MODE == 3 && wpos < end) {  // the search alone, its result kept alive
                 const int dc = pos - Q < LA + LB ? pos - Q : LA + LB;
-                r[0] ^= (KEY)(co_rank<KEY, S::MAXR, ZW>(s, A0, LA, B0, LB, dc, maxr) & 1);
+                r[0] ^= (KEY)(co_rank<KEY, S::MAXR, ZW, EQ>(s, A0, LA, B0, LB, dc, L, full) & 1);
             }
         } else if (wpos < end) {
             if constexpr (CH == 0)
-                merge_chain<KEY, IT, S::MAXR, ZW>(s, A0, LA, B0, LB, pos - Q, maxr, r);
+                merge_chain<KEY, IT, S::MAXR, ZW, EQ>(s, A0, LA, B0, LB, pos - Q, L, full, r);
             else
-                merge_chain_blk<KEY, IT, S::MAXR, ZW>(s, A0, LA, B0, LB, pos - Q, maxr, r);
+                merge_chain_blk<KEY, IT, S::MAXR, ZW, EQ>(s, A0, LA, B0, LB, pos - Q, L, full, r);
         }
         lds_barrier();
         if (lv < LK) {
