@@ -40,7 +40,13 @@ extern "C" {
  * library writes -0.0 before +0.0 within each rank's block; every position is
  * equal as a double and every non-zero position is bit-exact
  * (tests/test_gpu_parity.py::test_f64_signed_zeros_vs_reference). */
-enum misort_dtype { MISORT_U32 = 0, MISORT_U64 = 1, MISORT_F64 = 2 };
+/* MISORT_F32 keys are accepted by the key-value entry points only
+ * (misort_local_sort_pairs, misort_parallel_sort_pairs); every other entry
+ * point answers MISORT_E_INVALID for it.  Their order is the total order of
+ * the mapped 32-bit patterns (sign set: all bits inverted; else the sign bit
+ * set): -0.0 sorts before +0.0, negative NaNs sort first and positive NaNs
+ * last, and every output key is bit-identical to an input key. */
+enum misort_dtype { MISORT_U32 = 0, MISORT_U64 = 1, MISORT_F64 = 2, MISORT_F32 = 3 };
 
 enum misort_status {
     MISORT_OK = 0,
@@ -161,6 +167,36 @@ int misort_parallel_bitonic_sort_oop(misort_ctx* ctx, int dtype, const void* d_i
  * (d_in == d_out allowed). */
 int misort_local_sort(misort_ctx* ctx, int dtype, const void* d_in, void* d_out, int64_t n,
                       void* stream);
+
+/* ---- key-value sort (extension; the reference sorts bare keys) -------------- */
+
+/* Key-value sort on one GPU.  key_dtype MISORT_U32 or MISORT_F32; values are u32.
+ * Output: the n pairs ascending by (key, value), values compared unsigned.
+ * d_vals_in == NULL: the value of element i is i, so d_vals_out is the STABLE
+ * argsort of the keys (n <= 2^32).  d_keys_out == NULL: values only.
+ * Outputs may alias the corresponding inputs.  Asynchronous on `stream`.
+ *
+ * The pairs are sorted as 64-bit records (key << 32) | value through the path
+ * of misort_local_sort(MISORT_U64): the context keeps a record buffer and the
+ * sort's ping-pong buffer, 16 bytes per pair on top of the caller's arrays.
+ * The key and value arrays need 4-byte alignment only; 16-byte aligned ones
+ * take the faster vector kernels. */
+int misort_local_sort_pairs(misort_ctx* ctx, int key_dtype, const void* d_keys_in, const void* d_vals_in,
+                            void* d_keys_out, void* d_vals_out, int64_t n, void* stream);
+
+/* The same over the context's communicator (hypercube schedule, bracketed coded
+ * exchange, relay: the records travel as MISORT_U64 keys through the path of
+ * misort_parallel_bitonic_sort).  Rank r ends with pairs [r*loc, (r+1)*loc) of
+ * the global (key, value) order.  Every rank must pass the same loc_size:
+ * checked collectively, all ranks return MISORT_E_INVALID together otherwise
+ * (with unequal blocks psort.cc's compare-split keeps a rank's own count, so
+ * records would be duplicated or lost: tolerable for bare keys as the
+ * reference's documented defect, not for payloads).  d_vals_in == NULL: the
+ * value is the global index rank*loc + i (nranks*loc <= 2^32).  max_size as in
+ * misort_parallel_bitonic_sort. */
+int misort_parallel_sort_pairs(misort_ctx* ctx, int key_dtype, const void* d_keys_in, const void* d_vals_in,
+                               void* d_keys_out, void* d_vals_out, int64_t loc_size, int64_t max_size,
+                               void* stream);
 
 /* psort.cc:377-490 parallel_quick_sort (the reference binary's shipped sort,
  * called at psort.cc:647-648): d rounds of median-of-medians pivoting over

@@ -222,6 +222,17 @@ hipError_t f64_to_ord(uint64_t* a, int64_t n, hipStream_t s);
 hipError_t ord_to_f64(uint64_t* a, int64_t n, hipStream_t s);
 hipError_t ord_to_f64_copy(const uint64_t* a, uint64_t* b, int64_t n, hipStream_t s);  // b = f64 bits of a
 
+// Key-value records of the pair sort (pairs.hip): rec[i] = K(keys[i]) << 32 | v,
+// v = vals[i], or val_base + (uint32_t)i when vals is null; K is the identity
+// (u32 keys) or, f32, the 32-bit form of ord_of_f64.  unzip_pairs is the
+// inverse; a null `keys` writes the values only.  rec is 16-byte aligned; the
+// caller's arrays need 4-byte alignment only (16-byte aligned ones take the
+// vector kernel).  Records of KIND_OTHER with the bytes moved.
+hipError_t zip_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t val_base, uint64_t* rec, int64_t n,
+                     bool f32, hipStream_t s, LaunchHook* hook);
+hipError_t unzip_pairs(const uint64_t* rec, uint32_t* keys, uint32_t* vals, int64_t n, bool f32, hipStream_t s,
+                       LaunchHook* hook);
+
 // Counter-based SplitMix64 keys for global indices [g0, g0+n) (bench/test input).
 hipError_t fill_splitmix_u32(uint32_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);
 hipError_t fill_splitmix_u64(uint64_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);

@@ -775,6 +775,7 @@ struct misort_ctx {
     Transport* tr = nullptr;
     int nranks = 1, rank = 0;
     DevBuf work, recv, scratch, small, samp_me, samp_peer, pong;
+    DevBuf recs;  // key-value sort: the (key << 32 | value) records, 8 bytes per pair
     DevBuf qa, qb, qcnt;  // quick sort: current run, merge target, exchanged counts
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -1375,6 +1376,59 @@ int parallel_sort(misort_ctx* c, int dtype, const void* in, void* out, int64_t l
 // (high half) with the partner rank.  The reference re-sorts the whole buffer
 // each round (std::sort); the runs stay sorted here, so a device merge of the
 // kept part and the received part gives the same sequence.
+// ------------------------------------------------------------ key-value sort
+//
+// Pairs of a 32-bit key and a 32-bit value sort as the u64 records
+// (K(key) << 32) | value (pairs.hip): the record order is "by key, then by
+// value", so the sort between the zip and the unzip is the u64 path as it is.
+bool valid_pair_dtype(int dtype) { return dtype == MISORT_U32 || dtype == MISORT_F32; }
+constexpr int64_t kIndexValues = (int64_t)1 << 32;  // indices a 32-bit value can hold
+
+int zip_pairs(misort_ctx* c, int key_dtype, const void* keys, const void* vals, uint32_t val_base, int64_t n,
+              hipStream_t s) {
+    const hipError_t e = misort::zip_pairs((const uint32_t*)keys, (const uint32_t*)vals, val_base,
+                                           (uint64_t*)c->recs.p, n, key_dtype == MISORT_F32, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "zip_pairs: %s", hipGetErrorString(e));
+    return MISORT_OK;
+}
+
+int unzip_pairs(misort_ctx* c, int key_dtype, void* keys, void* vals, int64_t n, hipStream_t s) {
+    const hipError_t e = misort::unzip_pairs((const uint64_t*)c->recs.p, (uint32_t*)keys, (uint32_t*)vals, n,
+                                             key_dtype == MISORT_F32, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "unzip_pairs: %s", hipGetErrorString(e));
+    return MISORT_OK;
+}
+
+// The pair sort over the communicator: the records go through parallel_sort
+// as MISORT_U64 keys, in place in the context's record buffer.  Every rank
+// must hold the same number of pairs: with unequal blocks the compare-split
+// keeps a rank's own count (psort.cc:116-164), which would duplicate or drop
+// records.  The sizes are gathered first, so all ranks fail together before
+// the first exchange.
+int parallel_pairs(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in, void* keys_out,
+                   void* vals_out, int64_t loc, int64_t max_size, hipStream_t s) {
+    const int p = c->nranks;
+    if (p & (p - 1)) return fail(MISORT_E_NOT_POW2, "bitonic sort requires 2^d processors");
+    int rc;
+    if (p > 1) {
+        std::vector<int64_t> sizes;
+        if ((rc = c->tr->allgather_i64(&loc, 1, sizes, s))) return rc;
+        for (int r = 0; r < p; ++r)
+            if (sizes[r] != loc)
+                return fail(MISORT_E_INVALID, "pair sort needs equal blocks: rank %d holds %lld pairs, rank %d %lld", r,
+                            (long long)sizes[r], c->rank, (long long)loc);
+    }
+    if (!vals_in && loc > kIndexValues / p)
+        return fail(MISORT_E_INVALID, "argsort of %d x %lld keys: a 32-bit value holds 2^32 indices", p,
+                    (long long)loc);
+    if (loc == 0) return MISORT_OK;
+    if ((rc = c->recs.ensure((size_t)loc * sizeof(uint64_t)))) return rc;
+    // every pair is zipped before the sort reads a record: outputs may alias inputs
+    if ((rc = zip_pairs(c, key_dtype, keys_in, vals_in, (uint32_t)((int64_t)c->rank * loc), loc, s))) return rc;
+    if ((rc = parallel_sort(c, MISORT_U64, c->recs.p, c->recs.p, loc, max_size, s))) return rc;
+    return unzip_pairs(c, key_dtype, keys_out, vals_out, loc, s);
+}
+
 int parallel_quick(misort_ctx* c, int dtype, const void* in, int64_t loc, void* out, int64_t out_cap,
                    int64_t* out_n, hipStream_t s) {
     if (!valid_dtype(dtype)) return fail(MISORT_E_INVALID, "bad dtype %d", dtype);
@@ -1889,6 +1943,33 @@ int misort_local_sort(misort_ctx* c, int dtype, const void* in, void* out, int64
     hipStream_t s = pick(c, stream);
     // f64: mapped to ordered u64 by the first pass, back by the last
     return do_local_sort(c, dtype, in, out, n, dtype == MISORT_F64, s, nullptr, dtype == MISORT_F64);
+}
+
+int misort_local_sort_pairs(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in, void* keys_out,
+                            void* vals_out, int64_t n, void* stream) {
+    if (!c || !valid_pair_dtype(key_dtype) || n < 0 || (n > 0 && (!keys_in || !vals_out)))
+        return fail(MISORT_E_INVALID, "bad local_sort_pairs arguments");
+    if (!vals_in && n > kIndexValues)
+        return fail(MISORT_E_INVALID, "argsort of %lld keys: a 32-bit value holds 2^32 indices", (long long)n);
+    if (n == 0) return MISORT_OK;
+    hipStream_t s = pick(c, stream);
+    int rc = c->recs.ensure((size_t)n * sizeof(uint64_t));
+    if (rc) return rc;
+    // every pair is zipped before the sort reads a record: outputs may alias inputs
+    if ((rc = zip_pairs(c, key_dtype, keys_in, vals_in, 0, n, s))) return rc;
+    if ((rc = do_local_sort(c, MISORT_U64, c->recs.p, c->recs.p, n, false, s))) return rc;
+    return unzip_pairs(c, key_dtype, keys_out, vals_out, n, s);
+}
+
+int misort_parallel_sort_pairs(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in, void* keys_out,
+                               void* vals_out, int64_t loc, int64_t max_size, void* stream) {
+    if (!c) return fail(MISORT_E_INVALID, "null ctx");
+    if (c->nranks > 1 && !c->tr) return fail(MISORT_E_NO_COMM, "communicator not initialised");
+    if (!valid_pair_dtype(key_dtype) || loc < 0 || (loc > 0 && (!keys_in || !vals_out)))
+        return fail(MISORT_E_INVALID, "bad parallel_sort_pairs arguments");
+    const uint64_t calls0 = c->tr ? c->tr->calls : 0;
+    return collective_result(
+        c, calls0, parallel_pairs(c, key_dtype, keys_in, vals_in, keys_out, vals_out, loc, max_size, pick(c, stream)));
 }
 
 int misort_pass_probe(misort_ctx* c, int dtype, const void* in, void* out, int64_t n, int kind, int hi,

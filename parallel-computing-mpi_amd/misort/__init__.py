@@ -17,12 +17,13 @@ import ctypes
 import os
 
 __all__ = [
-    "U32", "U64", "F64", "MisortError", "NotPowerOfTwo", "NativeLibraryMissing",
+    "U32", "U64", "F64", "F32", "MisortError", "NotPowerOfTwo", "NativeLibraryMissing",
     "library_path", "lib", "Context", "Group", "block_sizes", "schedule", "tile_log2", "plan",
     "sample_indices", "exchange_count", "set_shared_gpu_env",
 ]
 
 U32, U64, F64 = 0, 1, 2
+F32 = 3  # keys of the key-value sorts only (Context.sort_pairs, argsort, parallel_sort_pairs)
 KIND_NAMES = ["tile_sort", "global_pass", "tile_merge", "merge_split", "other", "span_pass",
               "wide_pass", "run_merge", "exchange", "run_mergek", "run_mergek_kernel", "merge_split_tail"]
 
@@ -76,6 +77,8 @@ def lib():
         "misort_parallel_bitonic_sort": ([vp, i32, vp, i64, i64, vp], i32),
         "misort_parallel_bitonic_sort_oop": ([vp, i32, vp, vp, i64, i64, vp], i32),
         "misort_local_sort": ([vp, i32, vp, vp, i64, vp], i32),
+        "misort_local_sort_pairs": ([vp, i32, vp, vp, vp, vp, i64, vp], i32),
+        "misort_parallel_sort_pairs": ([vp, i32, vp, vp, vp, vp, i64, i64, vp], i32),
         "misort_merge_split": ([vp, i32, vp, i64, vp, i64, vp, i32, vp], i32),
         "misort_merge_split_tail": ([vp, i32, vp, i64, vp, i64, i32, vp], i32),
         "misort_parallel_quick_sort": ([vp, i32, vp, i64, vp, i64, ctypes.POINTER(i64), vp], i32),
@@ -236,6 +239,27 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _u32_storage(t):
+    import torch
+    return t.dtype == torch.int32 or (hasattr(torch, "uint32") and t.dtype == torch.uint32)
+
+
+def _pair_key_dtype(keys):
+    """Key type of the key-value sorts: uint32/int32 storage = u32, float32 = f32."""
+    import torch
+    if _u32_storage(keys):
+        return U32
+    if keys.dtype == torch.float32:
+        return F32
+    raise TypeError(f"unsupported key dtype {keys.dtype} (key-value sorts take u32/f32 keys)")
+
+
+def _pair_values(values, what="values"):
+    if values is not None and not _u32_storage(values):
+        raise TypeError(f"unsupported {what} dtype {values.dtype} (uint32/int32 storage)")
+    return values
+
+
 class Context:
     """One GPU (HIP device) = one reference MPI rank.
 
@@ -352,6 +376,68 @@ class Context:
         _check(lib().misort_local_sort(self._h, _dtype_of(inp), _ptr(inp), _ptr(out), n,
                                        self._stream(stream)))
         return out
+
+    # ---- key-value sort ----------------------------------------------------------
+    def _pair_outputs(self, keys, values, out_keys, out_values, n):
+        import torch
+        if out_values is None:  # indices of float keys: 32-bit integers of the keys' shape
+            like = values if values is not None else keys
+            out_values = torch.empty_like(like) if _u32_storage(like) else torch.empty_like(like, dtype=torch.int32)
+        _pair_values(out_values, "out_values")
+        if out_keys is not None and out_keys.dtype != keys.dtype:
+            raise TypeError(f"out_keys is {out_keys.dtype}, the keys are {keys.dtype}")
+        for t in (keys, values, out_keys, out_values):
+            if t is not None and (t.numel() < n or not t.is_contiguous()):
+                raise ValueError(f"a contiguous tensor of at least {n} elements is needed, got {tuple(t.shape)}")
+        return out_values
+
+    def sort_pairs(self, keys, values=None, out_keys=None, out_values=None, n=None, stream=None):
+        """Key-value sort on this GPU: the pairs ascending by (key, value), values
+        compared unsigned.  Keys are u32 (uint32/int32 storage) or float32 (total
+        order of the bit patterns: -0.0 before +0.0, negative NaNs first, positive
+        NaNs last); values are uint32/int32 storage.  ``values=None``: the value
+        of element i is i.  Outputs may be the inputs.  Returns ``(out_keys,
+        out_values)``."""
+        import torch
+        dt = _pair_key_dtype(keys)
+        _pair_values(values)
+        n = keys.numel() if n is None else int(n)
+        out_keys = torch.empty_like(keys) if out_keys is None else out_keys
+        out_values = self._pair_outputs(keys, values, out_keys, out_values, n)
+        _check(lib().misort_local_sort_pairs(self._h, dt, _ptr(keys), _ptr(values) if values is not None else None,
+                                             _ptr(out_keys), _ptr(out_values), n, self._stream(stream)))
+        return out_keys, out_values
+
+    def argsort(self, keys, out=None, n=None, stream=None):
+        """The stable argsort of u32 or float32 keys (order as in sort_pairs):
+        ``out[j]`` is the index of the j-th smallest key, equal keys in input
+        order.  No keys are written.  ``out`` is uint32/int32 storage (default:
+        a new tensor like u32 keys, int32 for float keys); the indices are
+        unsigned 32-bit patterns."""
+        dt = _pair_key_dtype(keys)
+        n = keys.numel() if n is None else int(n)
+        out = self._pair_outputs(keys, None, None, out, n)
+        _check(lib().misort_local_sort_pairs(self._h, dt, _ptr(keys), None, None, _ptr(out), n,
+                                             self._stream(stream)))
+        return out
+
+    def parallel_sort_pairs(self, keys, values=None, loc=None, max_size=None, out_keys=None, out_values=None,
+                            stream=None):
+        """sort_pairs over the communicator (the hypercube schedule of
+        parallel_bitonic_sort): rank r ends with pairs [r*loc, (r+1)*loc) of the
+        global (key, value) order.  Every rank passes the same ``loc`` (else every
+        rank raises MisortError, code -1).  ``values=None``: the value is the
+        global index rank*loc + i.  Returns ``(out_keys, out_values)``."""
+        import torch
+        dt = _pair_key_dtype(keys)
+        _pair_values(values)
+        loc = keys.numel() if loc is None else int(loc)
+        mx = 0 if max_size is None else int(max_size)
+        out_keys = torch.empty_like(keys) if out_keys is None else out_keys
+        out_values = self._pair_outputs(keys, values, out_keys, out_values, loc)
+        _check(lib().misort_parallel_sort_pairs(self._h, dt, _ptr(keys), _ptr(values) if values is not None else None,
+                                                _ptr(out_keys), _ptr(out_values), loc, mx, self._stream(stream)))
+        return out_keys, out_values
 
     def compare_split(self, local, recv, keep_max, out=None, stream=None, in_place_tail=False):
         """Device half of psort.cc:116-164 (no exchange).  in_place_tail: the
