@@ -40,9 +40,11 @@ extern "C" {
  * library writes -0.0 before +0.0 within each rank's block; every position is
  * equal as a double and every non-zero position is bit-exact
  * (tests/test_gpu_parity.py::test_f64_signed_zeros_vs_reference). */
-/* MISORT_F32 keys are accepted by the key-value entry points only
+/* MISORT_F32 keys are accepted by the 32-bit key-value entry points only
  * (misort_local_sort_pairs, misort_parallel_sort_pairs); every other entry
- * point answers MISORT_E_INVALID for it.  Their order is the total order of
+ * point, misort_local_sort_pairs64 included, answers MISORT_E_INVALID for it
+ * (64-bit keys with a payload, MISORT_U64 and MISORT_F64, go through
+ * misort_local_sort_pairs64).  Their order is the total order of
  * the mapped 32-bit patterns (sign set: all bits inverted; else the sign bit
  * set): -0.0 sorts before +0.0, negative NaNs sort first and positive NaNs
  * last, and every output key is bit-identical to an input key. */
@@ -170,7 +172,9 @@ int misort_local_sort(misort_ctx* ctx, int dtype, const void* d_in, void* d_out,
 
 /* ---- key-value sort (extension; the reference sorts bare keys) -------------- */
 
-/* Key-value sort on one GPU.  key_dtype MISORT_U32 or MISORT_F32; values are u32.
+/* Key-value sort on one GPU, 32-bit keys.  key_dtype MISORT_U32 or MISORT_F32
+ * (MISORT_U64 / MISORT_F64: MISORT_E_INVALID here, see misort_local_sort_pairs64
+ * below); values are u32.
  * Output: the n pairs ascending by (key, value), values compared unsigned.
  * d_vals_in == NULL: the value of element i is i, so d_vals_out is the STABLE
  * argsort of the keys (n <= 2^32).  d_keys_out == NULL: values only.
@@ -184,9 +188,43 @@ int misort_local_sort(misort_ctx* ctx, int dtype, const void* d_in, void* d_out,
 int misort_local_sort_pairs(misort_ctx* ctx, int key_dtype, const void* d_keys_in, const void* d_vals_in,
                             void* d_keys_out, void* d_vals_out, int64_t n, void* stream);
 
-/* The same over the context's communicator (hypercube schedule, bracketed coded
+/* Key-value sort on one GPU, 64-bit keys.  key_dtype MISORT_U64 or MISORT_F64
+ * (anything else: MISORT_E_INVALID); val_bytes is 4 or 8, values are opaque
+ * bit patterns.  Output: the n pairs ascending by key, EQUAL KEYS IN INPUT
+ * ORDER: a stable sort by key.  This differs from misort_local_sort_pairs'
+ * "(key, value)" order, because here the value is not part of a compared
+ * record: a 64-bit key leaves no room for it in the u64 records the sort moves,
+ * so the records carry the element's index and the values are gathered by it
+ * at the end.  f64 keys sort as misort_local_sort(MISORT_F64) sorts them:
+ * -0.0 before +0.0, negative NaNs first, positive NaNs last, and every output
+ * key is bit-identical to an input key (NaN payloads included).
+ * d_vals_in == NULL: d_vals_out receives n u32 indices, the stable argsort of
+ * the keys; val_bytes must then be 4.  d_keys_out == NULL: values or indices
+ * only.  0 <= n <= 2^32 (n == 0 launches nothing and looks at no pointer); d_keys_in and d_vals_out
+ * must be non-null for n > 0.  Asynchronous on `stream`.
+ *
+ * How: K(key), the order-preserving 64-bit pattern, is sorted as two halves,
+ * least significant first, each as distinct u64 records (half << 32 | 32-bit
+ * tag) through the path of misort_local_sort(MISORT_U64): first
+ * (lo(K) << 32 | i), then (hi(K) << 32 | rank of the first sort); a last
+ * kernel follows the two tags back to i and writes index, key and value.
+ * Scratch: two record buffers and the sort's ping-pong buffer, 24 bytes per
+ * pair on top of the caller's arrays, kept by the context.
+ *
+ * Aliasing: d_keys_out may be d_keys_in (the keys are last read before the
+ * second sort).  No output may overlap d_vals_in (the last kernel gathers from
+ * it while it writes), and d_keys_out must not overlap d_vals_out: both are
+ * checked by address range, MISORT_E_INVALID.  Keys need 8-byte alignment,
+ * values and indices their element's; 16-byte aligned arrays take the faster
+ * vector kernels. */
+int misort_local_sort_pairs64(misort_ctx* ctx, int key_dtype, const void* d_keys_in, const void* d_vals_in,
+                              int val_bytes, void* d_keys_out, void* d_vals_out, int64_t n, void* stream);
+
+/* misort_local_sort_pairs over the context's communicator, 32-bit keys only
+ * (there is no multi-rank sort of 64-bit keys with a payload: MISORT_U64 and
+ * MISORT_F64 are MISORT_E_INVALID here).  Hypercube schedule, bracketed coded
  * exchange, relay: the records travel as MISORT_U64 keys through the path of
- * misort_parallel_bitonic_sort).  Rank r ends with pairs [r*loc, (r+1)*loc) of
+ * misort_parallel_bitonic_sort.  Rank r ends with pairs [r*loc, (r+1)*loc) of
  * the global (key, value) order.  Every rank must pass the same loc_size:
  * checked collectively, all ranks return MISORT_E_INVALID together otherwise
  * (with unequal blocks psort.cc's compare-split keeps a rank's own count, so

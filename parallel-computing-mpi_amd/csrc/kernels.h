@@ -233,6 +233,24 @@ hipError_t zip_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t val_ba
 hipError_t unzip_pairs(const uint64_t* rec, uint32_t* keys, uint32_t* vals, int64_t n, bool f32, hipStream_t s,
                        LaunchHook* hook);
 
+// The three kernels around the two u64 sorts of the 64-bit key-value sort
+// (pairs.hip; K = ord_of_f64 for f64 keys, else the identity; n <= 2^32):
+//   zip_lo64     rec[i] = lo(K(keys[i])) << 32 | i;
+//   gather_hi64  rec[j] = hi(K(keys[s1[j] & 0xFFFFFFFF])) << 32 | j, s1 the sorted
+//                records of zip_lo64 (rec != s1);
+//   emit64       for output t, with j = s2[t] & 0xFFFFFFFF (s2: the sorted records
+//                of gather_hi64), r = s1[j], i = (uint32_t)r: keys_out[t] (if
+//                keys_out) = the key rebuilt from hi(s2[t]) and hi(r); vals_out[t]
+//                = vals_in[i] (val_bytes 4 or 8), or the u32 index i when vals_in
+//                is null (val_bytes 4).
+// rec, s1, s2 are 16-byte aligned; the caller's arrays need element alignment
+// only.  Records of KIND_OTHER: 16n, 24n and 16n + written bytes + gathered values.
+hipError_t zip_lo64(const uint64_t* keys, uint64_t* rec, int64_t n, bool f64, hipStream_t s, LaunchHook* hook);
+hipError_t gather_hi64(const uint64_t* s1, const uint64_t* keys, uint64_t* rec, int64_t n, bool f64, hipStream_t s,
+                       LaunchHook* hook);
+hipError_t emit64(const uint64_t* s2, const uint64_t* s1, const void* vals_in, int val_bytes, uint64_t* keys_out,
+                  void* vals_out, int64_t n, bool f64, hipStream_t s, LaunchHook* hook);
+
 // Counter-based SplitMix64 keys for global indices [g0, g0+n) (bench/test input).
 hipError_t fill_splitmix_u32(uint32_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);
 hipError_t fill_splitmix_u64(uint64_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);

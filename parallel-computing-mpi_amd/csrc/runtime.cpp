@@ -776,6 +776,7 @@ struct misort_ctx {
     int nranks = 1, rank = 0;
     DevBuf work, recv, scratch, small, samp_me, samp_peer, pong;
     DevBuf recs;  // key-value sort: the (key << 32 | value) records, 8 bytes per pair
+    DevBuf recs2;  // 64-bit keys: the second sort's records (recs holds the first's until the end)
     DevBuf qa, qb, qcnt;  // quick sort: current run, merge target, exchanged counts
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -1959,6 +1960,49 @@ int misort_local_sort_pairs(misort_ctx* c, int key_dtype, const void* keys_in, c
     if ((rc = zip_pairs(c, key_dtype, keys_in, vals_in, 0, n, s))) return rc;
     if ((rc = do_local_sort(c, MISORT_U64, c->recs.p, c->recs.p, n, false, s))) return rc;
     return unzip_pairs(c, key_dtype, keys_out, vals_out, n, s);
+}
+
+// 64-bit keys: two sorts of distinct u64 records, least-significant half of
+// K(key) first (pairs.hip).  recs holds the first sort's result until emit64
+// has read it; the second sort runs in recs2; both share the ping-pong buffer.
+int misort_local_sort_pairs64(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in, int val_bytes,
+                              void* keys_out, void* vals_out, int64_t n, void* stream) {
+    if (!c) return fail(MISORT_E_INVALID, "null ctx");
+    if (key_dtype != MISORT_U64 && key_dtype != MISORT_F64)
+        return fail(MISORT_E_INVALID, "local_sort_pairs64 takes MISORT_U64 or MISORT_F64 keys, got %d", key_dtype);
+    if (val_bytes != 4 && val_bytes != 8)
+        return fail(MISORT_E_INVALID, "values are 4 or 8 bytes, got %d", val_bytes);
+    if (n < 0 || n > kIndexValues || (n > 0 && (!keys_in || !vals_out)))
+        return fail(MISORT_E_INVALID, "bad local_sort_pairs64 arguments");
+    if (n == 0) return MISORT_OK;  // no array is looked at: empty ones may be null
+    if (!vals_in && val_bytes != 4)
+        return fail(MISORT_E_INVALID, "no d_vals_in: the output is u32 indices, val_bytes must be 4, got %d",
+                    val_bytes);
+    // emit64 gathers from vals_in while it writes both outputs
+    const auto overlap = [n](const void* a, int aw, const void* b, int bw) {
+        const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+        return a && b && a0 < b0 + (uint64_t)n * bw && b0 < a0 + (uint64_t)n * aw;
+    };
+    if (overlap(vals_out, val_bytes, vals_in, val_bytes) || overlap(keys_out, 8, vals_in, val_bytes))
+        return fail(MISORT_E_INVALID, "local_sort_pairs64: an output overlaps d_vals_in");
+    if (overlap(keys_out, 8, vals_out, val_bytes))
+        return fail(MISORT_E_INVALID, "local_sort_pairs64: d_keys_out overlaps d_vals_out");
+    hipStream_t s = pick(c, stream);
+    const size_t rec_bytes = std::max<size_t>(16, (size_t)n * sizeof(uint64_t));
+    int rc = c->recs.ensure(rec_bytes);
+    if (rc || (rc = c->recs2.ensure(rec_bytes))) return rc;
+    const bool f64 = key_dtype == MISORT_F64;
+    uint64_t *s1 = (uint64_t*)c->recs.p, *s2 = (uint64_t*)c->recs2.p;
+    hipError_t e = misort::zip_lo64((const uint64_t*)keys_in, s1, n, f64, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "zip_lo64: %s", hipGetErrorString(e));
+    if ((rc = do_local_sort(c, MISORT_U64, s1, s1, n, false, s))) return rc;
+    e = misort::gather_hi64(s1, (const uint64_t*)keys_in, s2, n, f64, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "gather_hi64: %s", hipGetErrorString(e));
+    if ((rc = do_local_sort(c, MISORT_U64, s2, s2, n, false, s))) return rc;
+    // the keys were last read by gather_hi64: keys_out may be keys_in
+    e = misort::emit64(s2, s1, vals_in, val_bytes, (uint64_t*)keys_out, vals_out, n, f64, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "emit64: %s", hipGetErrorString(e));
+    return MISORT_OK;
 }
 
 int misort_parallel_sort_pairs(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in, void* keys_out,

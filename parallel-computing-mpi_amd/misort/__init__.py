@@ -78,6 +78,7 @@ def lib():
         "misort_parallel_bitonic_sort_oop": ([vp, i32, vp, vp, i64, i64, vp], i32),
         "misort_local_sort": ([vp, i32, vp, vp, i64, vp], i32),
         "misort_local_sort_pairs": ([vp, i32, vp, vp, vp, vp, i64, vp], i32),
+        "misort_local_sort_pairs64": ([vp, i32, vp, vp, i32, vp, vp, i64, vp], i32),
         "misort_parallel_sort_pairs": ([vp, i32, vp, vp, vp, vp, i64, i64, vp], i32),
         "misort_merge_split": ([vp, i32, vp, i64, vp, i64, vp, i32, vp], i32),
         "misort_merge_split_tail": ([vp, i32, vp, i64, vp, i64, i32, vp], i32),
@@ -260,6 +261,22 @@ def _pair_values(values, what="values"):
     return values
 
 
+def _pair64_key_dtype(keys):
+    """Key type of the 64-bit key-value sort: uint64/int64 storage = u64, float64 = f64."""
+    import torch
+    if keys.dtype == torch.int64 or (hasattr(torch, "uint64") and keys.dtype == torch.uint64):
+        return U64
+    if keys.dtype == torch.float64:
+        return F64
+    raise TypeError(f"unsupported key dtype {keys.dtype} (sort_pairs64/argsort64 take u64/f64 keys)")
+
+
+def _pair64_check(n, **tensors):
+    for name, t in tensors.items():
+        if t is not None and (t.numel() < n or not t.is_contiguous()):
+            raise ValueError(f"{name}: a contiguous tensor of at least {n} elements is needed, got {tuple(t.shape)}")
+
+
 class Context:
     """One GPU (HIP device) = one reference MPI rank.
 
@@ -419,6 +436,48 @@ class Context:
         out = self._pair_outputs(keys, None, None, out, n)
         _check(lib().misort_local_sort_pairs(self._h, dt, _ptr(keys), None, None, _ptr(out), n,
                                              self._stream(stream)))
+        return out
+
+    def sort_pairs64(self, keys, values, out_keys=None, out_values=None, n=None, stream=None):
+        """Stable key-value sort of 64-bit keys on this GPU: the pairs ascending
+        by key, equal keys in input order (NOT sort_pairs' (key, value) order:
+        the values are never compared).  Keys are u64 (uint64/int64 storage,
+        compared unsigned) or float64 (order of local_sort: -0.0 before +0.0,
+        negative NaNs first, positive NaNs last, every key bit-exact); values
+        are any tensor of 4- or 8-byte elements, moved as bit patterns.
+        ``out_keys`` may be ``keys``; no output may overlap ``values`` and the
+        outputs must not overlap each other (MisortError, code -1).  Returns
+        ``(out_keys, out_values)``."""
+        import torch
+        dt = _pair64_key_dtype(keys)
+        if values.element_size() not in (4, 8):
+            raise TypeError(f"unsupported values dtype {values.dtype} (4- or 8-byte elements)")
+        n = keys.numel() if n is None else int(n)
+        out_keys = torch.empty_like(keys) if out_keys is None else out_keys
+        out_values = torch.empty_like(values) if out_values is None else out_values
+        if out_keys.dtype != keys.dtype:
+            raise TypeError(f"out_keys is {out_keys.dtype}, the keys are {keys.dtype}")
+        if out_values.dtype != values.dtype:
+            raise TypeError(f"out_values is {out_values.dtype}, the values are {values.dtype}")
+        _pair64_check(n, keys=keys, values=values, out_keys=out_keys, out_values=out_values)
+        _check(lib().misort_local_sort_pairs64(self._h, dt, _ptr(keys), _ptr(values), values.element_size(),
+                                               _ptr(out_keys), _ptr(out_values), n, self._stream(stream)))
+        return out_keys, out_values
+
+    def argsort64(self, keys, out=None, n=None, stream=None):
+        """The stable argsort of u64 or float64 keys (order as in sort_pairs64):
+        ``out[j]`` is the index of the j-th smallest key, equal keys in input
+        order.  No keys are written.  ``out`` is uint32/int32 storage (default:
+        a new int32 tensor of the keys' shape); the indices are unsigned 32-bit
+        patterns."""
+        import torch
+        dt = _pair64_key_dtype(keys)
+        n = keys.numel() if n is None else int(n)
+        out = torch.empty_like(keys, dtype=torch.int32) if out is None else out
+        _pair_values(out, "out")
+        _pair64_check(n, keys=keys, out=out)
+        _check(lib().misort_local_sort_pairs64(self._h, dt, _ptr(keys), None, 4, None, _ptr(out), n,
+                                               self._stream(stream)))
         return out
 
     def parallel_sort_pairs(self, keys, values=None, loc=None, max_size=None, out_keys=None, out_values=None,
