@@ -236,6 +236,47 @@ int misort_parallel_sort_pairs(misort_ctx* ctx, int key_dtype, const void* d_key
                                void* d_keys_out, void* d_vals_out, int64_t loc_size, int64_t max_size,
                                void* stream);
 
+/* ---- row-wise sort (extension; the reference sorts one array) ---------------- */
+
+/* Sorts every row of a row-major rows x cols array ascending, independently:
+ * d_out[r*cols .. r*cols+cols) = sorted d_in[r*cols .. r*cols+cols).
+ * dtype MISORT_U32, MISORT_U64 or MISORT_F64 (MISORT_F32: MISORT_E_INVALID); f64
+ * keys sort as misort_local_sort(MISORT_F64) sorts them: -0.0 before +0.0,
+ * negative NaNs first, positive NaNs last.  Every output key is bit-identical
+ * to an input key.  Rows are contiguous, row stride cols.  The arrays need
+ * element alignment only (a view one element into its storage, odd cols);
+ * 16-byte aligned ones whose cols is a multiple of 16 bytes of keys take the
+ * vector kernels.  d_out == d_in is allowed; any other overlap of the two
+ * rows*cols ranges is MISORT_E_INVALID, checked by address range before
+ * anything is launched.  rows == 0 or cols == 0 launches nothing and looks at
+ * no pointer; cols == 1 is a copy (nothing when in place).  MISORT_E_INVALID for
+ * negative sizes, a null context, or a null array with rows*cols > 0.
+ * Asynchronous on `stream`; a merge pass's rejected chunk (MISORT_E_INTERNAL)
+ * is reported by misort_synchronize, as for misort_local_sort.
+ *
+ * How (misort_rows_plan tells which):
+ *   cols <= 2^misort_tile_log2 (u32 2^15, u64/f64 2^13): ONE pass, one HBM read
+ *     and one write per key.  A SORT tile of 2^LT keys holds 2^(LT-LR) rows
+ *     padded virtually to 2^LR >= cols keys (LR >= 5: a row of up to 32 keys is
+ *     one lane's registers) and runs the network's levels 1..LR only.  No
+ *     scratch.
+ *   longer rows: every row is copied to a block of 2^k keys, k = ceil_log2(cols),
+ *     filled up with all-ones; the passes of a 2^k-key misort_local_sort run
+ *     over all rows*2^k keys, sorting every block on its own; the first cols
+ *     keys of every block are copied out.  Scratch kept by the context and
+ *     grown on demand: two buffers of rows*2^k keys, up to 4x the input's
+ *     bytes; just above a power of two the sort does up to 2x the work of
+ *     rows*cols keys. */
+int misort_local_sort_rows(misort_ctx* ctx, int dtype, const void* d_in, void* d_out,
+                           int64_t rows, int64_t cols, void* stream);
+
+/* Host only, no device: how a row sort of `cols` keys of key_bytes (4 or 8) runs.
+ * *path = 0: in one SORT pass (rows packed into LDS tiles); 1: padded blocks + merge passes.
+ * *tile_log2: the SORT tile; *block_log2: log2 of the padded row length;
+ * passes: as misort_plan.  Returns the number of passes or a negative status. */
+int misort_rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int* block_log2,
+                     int* passes, int max_passes);
+
 /* psort.cc:377-490 parallel_quick_sort (the reference binary's shipped sort,
  * called at psort.cc:647-648): d rounds of median-of-medians pivoting over
  * shrinking hypercube sub-groups, RCCL send/recv with the partner, device merge.

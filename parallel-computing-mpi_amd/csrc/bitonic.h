@@ -994,10 +994,12 @@ void launch_sort(const K* src, K* dst, int64_t n, bool ord_in, hipStream_t s, in
 
 template <typename K>
 hipError_t local_sort_impl(const K* in, K* out, int64_t n, bool ord_in, K* scratch, hipStream_t s,
-                           LaunchHook* hook, const StageIO* io, bool ord_out) {
+                           LaunchHook* hook, const StageIO* io, bool ord_out, int block_log2) {
     // merge passes ping-pong between out and scratch
     if (scratch == nullptr || scratch == out || scratch == in) return hipErrorInvalidValue;
-    const std::vector<Pass>& ps = plan_for<K>(n);
+    // block_log2 > 0: the plan of one block; every pass merges its groups of
+    // runs independently, and n is a multiple of the block, so no group is short
+    const std::vector<Pass>& ps = plan_for<K>(block_log2 > 0 ? (int64_t)1 << block_log2 : n);
     const int LT = ps[0].hi + 1;  // this plan's SORT tile
     const int np = (int)ps.size();
     const double bytes = 2.0 * (double)n * sizeof(K);
@@ -1084,12 +1086,14 @@ hipError_t local_sort_impl(const K* in, K* out, int64_t n, bool ord_in, K* scrat
 // Definition shared by sort_u32.hip / sort_u64.hip (one explicit instantiation each).
 template <typename K>
 hipError_t local_sort(const K* in, K* out, int64_t n, bool ord_in, K* scratch, hipStream_t s,
-                      LaunchHook* hook, const StageIO* io, bool ord_out) {
+                      LaunchHook* hook, const StageIO* io, bool ord_out, int block_log2) {
     if (n <= 0) return hipSuccess;
+    if (block_log2 < 0 || block_log2 > 62 || (block_log2 > 0 && (io || (n & (((int64_t)1 << block_log2) - 1)))))
+        return hipErrorInvalidValue;
     if (sizeof(K) == 4 && (ord_in || ord_out)) return hipErrorInvalidValue;
     // chunked output hands every chunk to after_last, which maps it itself
     if (ord_out && io && io->after_last) return hipErrorInvalidValue;
-    return local_sort_impl<K>(in, out, n, ord_in, scratch, s, hook, io, ord_out);
+    return local_sort_impl<K>(in, out, n, ord_in, scratch, s, hook, io, ord_out, block_log2);
 }
 
 // One pass of a plan's shape (probes and tests): the SORT tile pass over n keys

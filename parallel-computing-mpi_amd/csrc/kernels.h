@@ -91,9 +91,12 @@ struct StageIO {
 // ord_out (K = uint64_t): the output is mapped back to IEEE double bits --
 // by the last pass's stores when it is a multi-way pass, else by one more
 // sweep (small sorts).
+// block_log2 > 0 (the row sort's long rows): n is a multiple of 2^block_log2
+// and every aligned 2^block_log2-key block is sorted on its own -- the passes
+// are those of a 2^block_log2-key sort, run over all n keys (io must be null).
 template <typename K>
 hipError_t local_sort(const K* in, K* out, int64_t n, bool ord_in, K* scratch, hipStream_t s,
-                      LaunchHook* hook, const StageIO* io = nullptr, bool ord_out = false);
+                      LaunchHook* hook, const StageIO* io = nullptr, bool ord_out = false, int block_log2 = 0);
 
 // One HBM pass of a plan's shape over n keys (kind KIND_TILE_SORT, KIND_RUNS
 // or KIND_RUNSK; hi, R as in the plan): probes and tests.
@@ -250,6 +253,34 @@ hipError_t gather_hi64(const uint64_t* s1, const uint64_t* keys, uint64_t* rec, 
                        LaunchHook* hook);
 hipError_t emit64(const uint64_t* s2, const uint64_t* s1, const void* vals_in, int val_bytes, uint64_t* keys_out,
                   void* vals_out, int64_t n, bool f64, hipStream_t s, LaunchHook* hook);
+
+// Row-wise sort (rows_tile.h, rows.hip): every row of a row-major rows x cols
+// array ascending, on its own.
+//   sort_rows_tile  cols <= 2^tile_log2: one SORT pass, 2^(LT - LR) rows of
+//                   2^LR >= cols virtual keys per LDS tile (in == out allowed;
+//                   element alignment).  f64 (K = uint64_t): IEEE double bits in
+//                   and out.  One KIND_TILE_SORT record of 2 rows cols keys.
+//   pad_rows        pad[r << k | c] = K(in[r cols + c]) for c < cols, all-ones
+//                   for cols <= c < 2^k (K = ord_of_f64 for f64 keys);
+//   unpad_rows      out[r cols + c] = unK(pad[r << k | c]) for c < cols.
+// pad is 16-byte aligned, 2^k >= 16 bytes of keys; the caller's arrays need
+// element alignment only.  Records of KIND_OTHER, each counted as
+// (rows cols + rows 2^k) keys (unpad skips the vectors that hold padding only).
+template <typename K>
+hipError_t sort_rows_tile(const K* in, K* out, int64_t rows, int64_t cols, bool f64, hipStream_t s,
+                          LaunchHook* hook);
+hipError_t pad_rows(const void* in, void* pad, int64_t rows, int64_t cols, int k, int key_bytes, bool f64,
+                    hipStream_t s, LaunchHook* hook);
+hipError_t unpad_rows(const void* pad, void* out, int64_t rows, int64_t cols, int k, int key_bytes, bool f64,
+                      hipStream_t s, LaunchHook* hook);
+// How a row sort of `cols` keys runs (host only): *path 0 = sort_rows_tile
+// (*block_log2 = LR, *tile_log2 = LT, one KIND_TILE_SORT record), 1 = padded
+// blocks (*block_log2 = ceil_log2(cols), the passes of plan_passes(2^block_log2)).
+// Records as plan_passes; returns the count.
+int rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int* block_log2, int* out, int max);
+// Rows shorter than 2^ROWS_LR_MIN keys are sorted as 2^ROWS_LR_MIN virtual keys
+// (one lane's registers).
+constexpr int ROWS_LR_MIN = 5;
 
 // Counter-based SplitMix64 keys for global indices [g0, g0+n) (bench/test input).
 hipError_t fill_splitmix_u32(uint32_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);

@@ -1,0 +1,194 @@
+// rows.hip -- the long-row path of the row-wise sort (gfx950) and its plan.
+//
+// A row longer than the largest SORT tile is sorted as a block of 2^k keys,
+// k = ceil_log2(cols): pad_rows copies every row to the start of its block and
+// fills the rest with all-ones, the passes of a 2^k-key local sort run over
+// the rows * 2^k keys (local_sort's block_log2: every pass merges its groups of
+// runs on their own, so every aligned block is sorted), and unpad_rows writes
+// the first cols keys of every block back.  The all-ones suffix of a block
+// sorts to its end, whatever real keys equal it.
+//
+// f64 keys are mapped to ordered u64 HERE, in the two kernels, and the sort
+// between them runs on plain u64: the SORT tile's own f64 load would map the
+// raw all-ones padding (a negative NaN pattern) to 0, the smallest key.
+//
+// Both kernels are HBM-bound and shaped like pairs.hip's: 256 lanes, a capped
+// grid that strides over the rest, 64-bit indices, one 16-byte vector of the
+// padded buffer per lane and trip.  The padded buffer is the context's own and
+// 16-byte aligned; the caller's array is only known to be element-aligned, so
+// the launchers take the vector kernel when it is 16-byte aligned and cols is a
+// multiple of the vector (every vector then lies inside one row), else element
+// accesses on the caller's side.
+#include "kernels.h"
+
+namespace misort {
+
+namespace {
+
+constexpr int ROWS_NT = 256;
+// one trip per lane up to 2^28 vectors, as the 64-bit pair kernels (pairs.hip)
+constexpr int ROWS_MAX_GRID = 1 << 20;
+
+template <typename K>
+struct RowVec {
+    static constexpr int V = 16 / (int)sizeof(K);
+    typedef K type __attribute__((ext_vector_type(V)));
+};
+
+template <typename K, bool VEC, bool F64>
+__global__ __launch_bounds__(ROWS_NT) void k_pad_rows(const K* __restrict__ in, K* __restrict__ padded, int64_t rows,
+                                                      int64_t cols, int k) {
+    constexpr int V = RowVec<K>::V;
+    typedef typename RowVec<K>::type vec_t;
+    const int64_t nq = (rows << k) / V, cm = ((int64_t)1 << k) - 1;
+    const int64_t stride = (int64_t)gridDim.x * ROWS_NT;
+    for (int64_t q = (int64_t)blockIdx.x * ROWS_NT + threadIdx.x; q < nq; q += stride) {
+        const int64_t p = q * V, r = p >> k, c = p & cm;
+        const K* src = in + (r * cols + c);
+        vec_t x = {};
+        if constexpr (VEC) {
+            // cols % V == 0: the whole vector is real or none of it
+            if (c < cols) x = *reinterpret_cast<const vec_t*>(src);
+#pragma unroll
+            for (int j = 0; j < V; ++j) x[j] = c >= cols ? ~(K)0 : F64 ? (K)ord_of_f64((uint64_t)x[j]) : x[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                K y = ~(K)0;
+                if (c + j < cols) y = F64 ? (K)ord_of_f64((uint64_t)src[j]) : src[j];
+                x[j] = y;
+            }
+        }
+        reinterpret_cast<vec_t*>(padded)[q] = x;
+    }
+}
+
+template <typename K, bool VEC, bool F64>
+__global__ __launch_bounds__(ROWS_NT) void k_unpad_rows(const K* __restrict__ padded, K* __restrict__ out,
+                                                        int64_t rows, int64_t cols, int k) {
+    constexpr int V = RowVec<K>::V;
+    typedef typename RowVec<K>::type vec_t;
+    const int64_t nq = (rows << k) / V, cm = ((int64_t)1 << k) - 1;
+    const int64_t stride = (int64_t)gridDim.x * ROWS_NT;
+    for (int64_t q = (int64_t)blockIdx.x * ROWS_NT + threadIdx.x; q < nq; q += stride) {
+        const int64_t p = q * V, r = p >> k, c = p & cm;
+        if (c >= cols) continue;  // padding only: not read
+        vec_t x = reinterpret_cast<const vec_t*>(padded)[q];
+        if constexpr (F64) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) x[j] = (K)f64_of_ord((uint64_t)x[j]);
+        }
+        K* dst = out + (r * cols + c);
+        if constexpr (VEC) {
+            *reinterpret_cast<vec_t*>(dst) = x;
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                if (c + j < cols) dst[j] = x[j];
+        }
+    }
+}
+
+unsigned rows_grid(int64_t nq) {
+    const int64_t g = (nq + ROWS_NT - 1) / ROWS_NT;
+    return (unsigned)(g < 1 ? 1 : g > ROWS_MAX_GRID ? ROWS_MAX_GRID : g);
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+struct OtherScope {  // the launch's KIND_OTHER record
+    LaunchHook* h;
+    hipStream_t s;
+    OtherScope(LaunchHook* h_, double bytes, hipStream_t s_) : h(h_), s(s_) {
+        if (h) h->before(KIND_OTHER, bytes, s);
+    }
+    ~OtherScope() {
+        if (h) h->after(KIND_OTHER, s);
+    }
+};
+
+// the arguments both kernels share; k >= 2 keeps a block a whole number of vectors
+bool rows_args_ok(const void* user, const void* padded, int64_t rows, int64_t cols, int k, int key_bytes, bool f64) {
+    if (!user || !padded || !aligned16(padded) || (key_bytes != 4 && key_bytes != 8) || (f64 && key_bytes != 8))
+        return false;
+    return k >= 2 && k <= 62 && cols <= ((int64_t)1 << k) && rows <= (INT64_MAX >> k) / key_bytes;
+}
+
+double rows_bytes(int64_t rows, int64_t cols, int k, int key_bytes) {
+    return ((double)rows * (double)cols + (double)rows * (double)((int64_t)1 << k)) * key_bytes;
+}
+
+template <typename K, bool PAD>
+void launch_rows_copy(const void* src, void* dst, int64_t rows, int64_t cols, int k, bool vec, bool f64,
+                      hipStream_t s) {
+    const unsigned g = rows_grid((rows << k) / RowVec<K>::V);
+    const K* a = (const K*)src;
+    K* b = (K*)dst;
+#define MISORT_ROWS_LAUNCH(VEC_, F64_)                                                      \
+    do {                                                                                    \
+        if constexpr (PAD) k_pad_rows<K, VEC_, F64_><<<g, ROWS_NT, 0, s>>>(a, b, rows, cols, k); \
+        else k_unpad_rows<K, VEC_, F64_><<<g, ROWS_NT, 0, s>>>(a, b, rows, cols, k);        \
+    } while (0)
+    if constexpr (sizeof(K) == 8) {
+        if (vec && f64) MISORT_ROWS_LAUNCH(true, true);
+        else if (vec) MISORT_ROWS_LAUNCH(true, false);
+        else if (f64) MISORT_ROWS_LAUNCH(false, true);
+        else MISORT_ROWS_LAUNCH(false, false);
+    } else {
+        (void)f64;
+        if (vec) MISORT_ROWS_LAUNCH(true, false);
+        else MISORT_ROWS_LAUNCH(false, false);
+    }
+#undef MISORT_ROWS_LAUNCH
+}
+
+}  // namespace
+
+hipError_t pad_rows(const void* in, void* padded, int64_t rows, int64_t cols, int k, int key_bytes, bool f64,
+                    hipStream_t s, LaunchHook* hook) {
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    if (!rows_args_ok(in, padded, rows, cols, k, key_bytes, f64)) return hipErrorInvalidValue;
+    const bool vec = aligned16(in) && cols % (16 / key_bytes) == 0;
+    OtherScope os(hook, rows_bytes(rows, cols, k, key_bytes), s);
+    if (key_bytes == 4) launch_rows_copy<uint32_t, true>(in, padded, rows, cols, k, vec, false, s);
+    else launch_rows_copy<uint64_t, true>(in, padded, rows, cols, k, vec, f64, s);
+    return hipGetLastError();
+}
+
+hipError_t unpad_rows(const void* padded, void* out, int64_t rows, int64_t cols, int k, int key_bytes, bool f64,
+                      hipStream_t s, LaunchHook* hook) {
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    if (!rows_args_ok(out, padded, rows, cols, k, key_bytes, f64)) return hipErrorInvalidValue;
+    const bool vec = aligned16(out) && cols % (16 / key_bytes) == 0;
+    OtherScope os(hook, rows_bytes(rows, cols, k, key_bytes), s);
+    if (key_bytes == 4) launch_rows_copy<uint32_t, false>(padded, out, rows, cols, k, vec, false, s);
+    else launch_rows_copy<uint64_t, false>(padded, out, rows, cols, k, vec, f64, s);
+    return hipGetLastError();
+}
+
+int rows_plan(int64_t cols, int key_bytes, int* path, int* tile, int* block, int* out, int max) {
+    const int lt = tile_log2(key_bytes);
+    int k = 0;
+    while (k < 62 && ((int64_t)1 << k) < cols) ++k;
+    if (cols <= ((int64_t)1 << lt)) {
+        // one SORT pass: 2^(tile - block) rows per tile, levels 1..block
+        const int lr = k < ROWS_LR_MIN ? ROWS_LR_MIN : k;
+        *path = 0;
+        *block = lr;
+        *tile = key_bytes == 4 && lr < SORT_LT_U32 ? SORT_LT_MERGE : lt;
+        if (max > 0) {
+            out[0] = KIND_TILE_SORT;
+            out[1] = *tile - 1;
+            out[2] = out[3] = 0;
+        }
+        return 1;
+    }
+    *path = 1;
+    *block = k;
+    int first[4] = {KIND_TILE_SORT, lt - 1, 0, 0};
+    const int np = plan_passes((int64_t)1 << k, key_bytes, max > 0 ? out : first, max > 0 ? max : 1);
+    *tile = (max > 0 ? out[1] : first[1]) + 1;
+    return np;
+}
+
+}  // namespace misort

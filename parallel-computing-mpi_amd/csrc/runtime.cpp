@@ -777,6 +777,7 @@ struct misort_ctx {
     DevBuf work, recv, scratch, small, samp_me, samp_peer, pong;
     DevBuf recs;  // key-value sort: the (key << 32 | value) records, 8 bytes per pair
     DevBuf recs2;  // 64-bit keys: the second sort's records (recs holds the first's until the end)
+    DevBuf rowpad;  // row sort of long rows: every row padded to a 2^k-key block
     DevBuf qa, qb, qcnt;  // quick sort: current run, merge target, exchanged counts
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -2003,6 +2004,67 @@ int misort_local_sort_pairs64(misort_ctx* c, int key_dtype, const void* keys_in,
     e = misort::emit64(s2, s1, vals_in, val_bytes, (uint64_t*)keys_out, vals_out, n, f64, s, hook(c));
     if (e != hipSuccess) return fail(MISORT_E_HIP, "emit64: %s", hipGetErrorString(e));
     return MISORT_OK;
+}
+
+// Rows up to the largest SORT tile: one pass of row tiles (rows_tile.h).  Longer
+// rows: padded to blocks of 2^k keys in rowpad, sorted there block by block with
+// the ping-pong buffer as scratch, and cut back to cols keys (rows.hip).
+int misort_local_sort_rows(misort_ctx* c, int dtype, const void* in, void* out, int64_t rows, int64_t cols,
+                           void* stream) {
+    if (!c) return fail(MISORT_E_INVALID, "null ctx");
+    if (!valid_dtype(dtype))
+        return fail(MISORT_E_INVALID, "local_sort_rows takes MISORT_U32, MISORT_U64 or MISORT_F64 keys, got %d", dtype);
+    if (rows < 0 || cols < 0) return fail(MISORT_E_INVALID, "bad local_sort_rows arguments");
+    if (rows == 0 || cols == 0) return MISORT_OK;  // no array is looked at: empty ones may be null
+    const size_t kb = key_bytes(dtype);
+    int k = 0;  // ceil_log2(cols)
+    while (k < 62 && ((int64_t)1 << k) < cols) ++k;
+    // the padded blocks of the long-row path must be addressable too
+    if (k >= 60 || rows > (INT64_MAX >> (k + 4)))
+        return fail(MISORT_E_INVALID, "local_sort_rows: %lld x %lld keys are too many", (long long)rows, (long long)cols);
+    if (!in || !out) return fail(MISORT_E_INVALID, "bad local_sort_rows arguments");
+    const uint64_t bytes = (uint64_t)rows * (uint64_t)cols * kb;
+    const uintptr_t a0 = (uintptr_t)in, b0 = (uintptr_t)out;
+    // a tile or a pad sweep reads rows another workgroup may already have rewritten
+    if (a0 != b0 && a0 < b0 + bytes && b0 < a0 + bytes)
+        return fail(MISORT_E_INVALID, "local_sort_rows: d_out overlaps d_in (only d_out == d_in is allowed)");
+    hipStream_t s = pick(c, stream);
+    const bool f64 = dtype == MISORT_F64;
+    if (cols == 1) {
+        if (in != out) HIPCHK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, s));
+        return MISORT_OK;
+    }
+    hipError_t e;
+    if (k <= misort::tile_log2((int)kb)) {
+        e = kb == 4 ? misort::sort_rows_tile<uint32_t>((const uint32_t*)in, (uint32_t*)out, rows, cols, false, s, hook(c))
+                    : misort::sort_rows_tile<uint64_t>((const uint64_t*)in, (uint64_t*)out, rows, cols, f64, s, hook(c));
+        if (e != hipSuccess) return fail(MISORT_E_HIP, "sort_rows_tile: %s", hipGetErrorString(e));
+        return MISORT_OK;
+    }
+    const int64_t n = rows << k;
+    int rc = c->rowpad.ensure((size_t)n * kb);
+    if (rc || (rc = c->pong.ensure((size_t)n * kb))) return rc;
+    e = misort::pad_rows(in, c->rowpad.p, rows, cols, k, (int)kb, f64, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "pad_rows: %s", hipGetErrorString(e));
+    // plain u64 between the two kernels: they map f64 keys themselves
+    if (kb == 4)
+        e = misort::local_sort<uint32_t>((const uint32_t*)c->rowpad.p, (uint32_t*)c->rowpad.p, n, false,
+                                         (uint32_t*)c->pong.p, s, hook(c), nullptr, false, k);
+    else
+        e = misort::local_sort<uint64_t>((const uint64_t*)c->rowpad.p, (uint64_t*)c->rowpad.p, n, false,
+                                         (uint64_t*)c->pong.p, s, hook(c), nullptr, false, k);
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "local_sort (row blocks): %s", hipGetErrorString(e));
+    e = misort::unpad_rows(c->rowpad.p, out, rows, cols, k, (int)kb, f64, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "unpad_rows: %s", hipGetErrorString(e));
+    return MISORT_OK;
+}
+
+int misort_rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int* block_log2, int* passes,
+                     int max_passes) {
+    if (key_bytes != 4 && key_bytes != 8) return fail(MISORT_E_INVALID, "key_bytes must be 4 or 8");
+    if (cols < 0 || !path || !tile_log2 || !block_log2) return fail(MISORT_E_INVALID, "bad rows_plan arguments");
+    if (max_passes > 0 && !passes) return fail(MISORT_E_INVALID, "null passes");
+    return misort::rows_plan(cols, key_bytes, path, tile_log2, block_log2, passes, max_passes < 0 ? 0 : max_passes);
 }
 
 int misort_parallel_sort_pairs(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in, void* keys_out,

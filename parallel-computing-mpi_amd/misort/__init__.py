@@ -19,7 +19,7 @@ import os
 __all__ = [
     "U32", "U64", "F64", "F32", "MisortError", "NotPowerOfTwo", "NativeLibraryMissing",
     "library_path", "lib", "Context", "Group", "block_sizes", "schedule", "tile_log2", "plan",
-    "sample_indices", "exchange_count", "set_shared_gpu_env",
+    "sample_indices", "exchange_count", "set_shared_gpu_env", "rows_plan",
 ]
 
 U32, U64, F64 = 0, 1, 2
@@ -80,6 +80,9 @@ def lib():
         "misort_local_sort_pairs": ([vp, i32, vp, vp, vp, vp, i64, vp], i32),
         "misort_local_sort_pairs64": ([vp, i32, vp, vp, i32, vp, vp, i64, vp], i32),
         "misort_parallel_sort_pairs": ([vp, i32, vp, vp, vp, vp, i64, i64, vp], i32),
+        "misort_local_sort_rows": ([vp, i32, vp, vp, i64, i64, vp], i32),
+        "misort_rows_plan": ([i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32),
+                              ctypes.POINTER(i32), i32], i32),
         "misort_merge_split": ([vp, i32, vp, i64, vp, i64, vp, i32, vp], i32),
         "misort_merge_split_tail": ([vp, i32, vp, i64, vp, i64, i32, vp], i32),
         "misort_parallel_quick_sort": ([vp, i32, vp, i64, vp, i64, ctypes.POINTER(i64), vp], i32),
@@ -180,6 +183,21 @@ def plan(n, key_bytes=4):
     lib().misort_plan(n, key_bytes, buf, np_)
     return [(KIND_NAMES[buf[4 * i]], buf[4 * i + 1], buf[4 * i + 2], bool(buf[4 * i + 3]))
             for i in range(np_)]
+
+
+def rows_plan(cols, key_bytes=4):
+    """How Context.sort_rows sorts rows of `cols` keys: ``{"path": "tile" (one
+    SORT pass, 2^(tile_log2 - block_log2) rows per LDS tile) | "blocks" (rows
+    padded to 2^block_log2 keys, then the passes of plan(2^block_log2)),
+    "tile_log2", "block_log2", "passes": [(kind_name, hi, R, flip)]}``."""
+    path, tile, block = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    refs = (ctypes.byref(path), ctypes.byref(tile), ctypes.byref(block))
+    np_ = _check(lib().misort_rows_plan(cols, key_bytes, *refs, None, 0))
+    buf = (ctypes.c_int32 * (4 * max(np_, 1)))()
+    _check(lib().misort_rows_plan(cols, key_bytes, *refs, buf, np_))
+    return {"path": ("tile", "blocks")[path.value], "tile_log2": tile.value, "block_log2": block.value,
+            "passes": [(KIND_NAMES[buf[4 * i]], buf[4 * i + 1], buf[4 * i + 2], bool(buf[4 * i + 3]))
+                       for i in range(np_)]}
 
 
 class Group:
@@ -392,6 +410,32 @@ class Context:
         n = inp.numel() if n is None else int(n)
         _check(lib().misort_local_sort(self._h, _dtype_of(inp), _ptr(inp), _ptr(out), n,
                                        self._stream(stream)))
+        return out
+
+    def sort_rows(self, inp, out=None, stream=None):
+        """Sorts along the last dimension of a contiguous tensor of any rank >= 1:
+        every row of ``shape[-1]`` keys ascending, on its own (u32/u64/f64 keys
+        as in local_sort; f64: -0.0 before +0.0, negative NaNs first, positive
+        NaNs last, every key bit-exact).  The default is a NEW tensor, the input
+        is left unchanged; ``out=inp`` sorts in place and returns ``inp``.  Any
+        other overlap of ``out`` with ``inp`` is a MisortError (code -1).  A
+        non-contiguous tensor and a too-small ``out`` raise ValueError, an
+        ``out`` of another dtype TypeError."""
+        import torch
+        dt = _dtype_of(inp)
+        if inp.dim() < 1:
+            raise ValueError("sort_rows needs a tensor of rank >= 1")
+        if not inp.is_contiguous():
+            raise ValueError(f"sort_rows needs a contiguous tensor, got strides {tuple(inp.stride())}")
+        out = torch.empty_like(inp) if out is None else out
+        if out.dtype != inp.dtype:
+            raise TypeError(f"out is {out.dtype}, the input is {inp.dtype}")
+        if out.numel() < inp.numel() or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous tensor of at least {inp.numel()} elements is needed, "
+                             f"got {tuple(out.shape)}")
+        cols = inp.shape[-1]
+        rows = inp.numel() // cols if cols else 0
+        _check(lib().misort_local_sort_rows(self._h, dt, _ptr(inp), _ptr(out), rows, cols, self._stream(stream)))
         return out
 
     # ---- key-value sort ----------------------------------------------------------
