@@ -270,6 +270,48 @@ int misort_parallel_sort_pairs(misort_ctx* ctx, int key_dtype, const void* d_key
 int misort_local_sort_rows(misort_ctx* ctx, int dtype, const void* d_in, void* d_out,
                            int64_t rows, int64_t cols, void* stream);
 
+/* Row-wise key-value sort, 32-bit keys: every row of the row-major rows x cols
+ * arrays d_keys_in / d_vals_in is sorted on its own, ascending by (key, value),
+ * values compared unsigned: exactly the order of misort_local_sort_pairs, row by
+ * row.  key_dtype MISORT_U32 or MISORT_F32 (anything else: MISORT_E_INVALID;
+ * 64-bit keys would need 128-bit records); values are 32-bit patterns.  f32
+ * keys sort in the total order of their bit patterns: -0.0 before +0.0,
+ * negative NaNs first, positive NaNs last; every output key is bit-identical to
+ * an input key.
+ * d_vals_in == NULL: the value of element (r, c) is c, so d_vals_out holds the
+ * STABLE row-wise argsort, equal keys in column order (cols <= 2^32).
+ * d_keys_out == NULL: no keys are written.  d_keys_in and d_vals_out are
+ * required when rows*cols > 0.  rows == 0 or cols == 0 launches nothing and
+ * looks at no pointer; cols == 1 copies keys and values (argsort: zeros).
+ * MISORT_E_INVALID for negative sizes and a null context (checked first).
+ * The arrays need 4-byte alignment only; when every array in use is 16-byte
+ * aligned and cols is a multiple of 4 the one-pass kernel takes 16-byte
+ * accesses, when 8-byte aligned and cols is even 8-byte ones.  Asynchronous on
+ * `stream`; a merge pass's rejected chunk (MISORT_E_INTERNAL) is reported by
+ * misort_synchronize, as for misort_local_sort.
+ *
+ * Aliasing: d_keys_out == d_keys_in and d_vals_out == d_vals_in (the same base
+ * pointer) sort in place.  Any other overlap among the four rows*cols*4-byte
+ * ranges, the two outputs with each other included, is MISORT_E_INVALID,
+ * checked by address range before anything is launched.
+ *
+ * How (misort_rows_plan(cols, 8) tells which: the pairs travel as the u64
+ * records (K(key) << 32) | value of misort_local_sort_pairs):
+ *   cols <= 2^13: ONE pass of the u64 row tile of misort_local_sort_rows.  The
+ *     record is formed in registers as the tile loads and split as it stores,
+ *     so each array element is read once and written once and no record ever
+ *     lies in HBM.  No scratch.
+ *   longer rows: the padded blocks of misort_local_sort_rows on records.  The
+ *     pad sweep forms the records (all-ones above cols), the passes of a
+ *     2^k-key u64 sort, k = ceil_log2(cols), run over all rows*2^k records, the
+ *     unpad sweep splits the first cols records of every block into the two
+ *     outputs.  Scratch kept by the context and grown on demand: two buffers
+ *     of rows*2^k*8 bytes. */
+int misort_local_sort_rows_pairs(misort_ctx* ctx, int key_dtype,
+                                 const void* d_keys_in, const void* d_vals_in,
+                                 void* d_keys_out, void* d_vals_out,
+                                 int64_t rows, int64_t cols, void* stream);
+
 /* Host only, no device: how a row sort of `cols` keys of key_bytes (4 or 8) runs.
  * *path = 0: in one SORT pass (rows packed into LDS tiles); 1: padded blocks + merge passes.
  * *tile_log2: the SORT tile; *block_log2: log2 of the padded row length;

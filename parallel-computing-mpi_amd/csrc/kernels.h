@@ -17,6 +17,10 @@ __device__ __forceinline__ uint64_t ord_of_f64(uint64_t b) {
 __device__ __forceinline__ uint64_t f64_of_ord(uint64_t o) {
     return (o >> 63) ? (o & 0x7FFFFFFFFFFFFFFFull) : ~o;
 }
+// The same on 32 bits: IEEE float bits <-> order-preserving u32 (the f32 keys
+// of the key-value sorts).
+__device__ __forceinline__ uint32_t ord_of_f32(uint32_t b) { return (b >> 31) ? ~b : (b | 0x80000000u); }
+__device__ __forceinline__ uint32_t f32_of_ord(uint32_t o) { return (o >> 31) ? (o & 0x7FFFFFFFu) : ~o; }
 
 // Kernel families, used for per-launch profiling (HIP events) and reporting.
 enum Kind : int {
@@ -273,6 +277,29 @@ hipError_t pad_rows(const void* in, void* pad, int64_t rows, int64_t cols, int k
                     hipStream_t s, LaunchHook* hook);
 hipError_t unpad_rows(const void* pad, void* out, int64_t rows, int64_t cols, int k, int key_bytes, bool f64,
                       hipStream_t s, LaunchHook* hook);
+// Row-wise key-value sort of 32-bit keys with 32-bit values (rows_pairs.hip,
+// rows.hip): every row ascending by the record K(key) << 32 | value, K the
+// identity or (f32) ord_of_f32.  vals_in null: the value of (r, c) is c;
+// keys_out null: no keys are written.  An output may be exactly an input.
+//   sort_rows_pairs_tile  cols <= 2^13: the u64 row tile with the record formed
+//                   in registers as the tile loads and split as it stores.  One
+//                   KIND_TILE_SORT record of the bytes of the arrays in use
+//                   (4 rows cols each).  Element alignment; 16-byte accesses
+//                   when every array in use is 16-byte aligned and cols is a
+//                   multiple of 4, 8-byte ones when 8-byte aligned and cols even.
+//   pad_rows_pairs  pad[r << k | c] = the record of (r, c) for c < cols,
+//                   all-ones for cols <= c < 2^k;
+//   unpad_rows_pairs  keys_out / vals_out[r cols + c] from pad[r << k | c], c < cols.
+// pad is 16-byte aligned, k >= 1.  Records of KIND_OTHER: pad counts the caller's
+// arrays it reads and rows 2^k records, unpad rows cols records and the arrays
+// it writes.
+hipError_t sort_rows_pairs_tile(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out,
+                                uint32_t* vals_out, int64_t rows, int64_t cols, bool f32, hipStream_t s,
+                                LaunchHook* hook);
+hipError_t pad_rows_pairs(const uint32_t* keys_in, const uint32_t* vals_in, uint64_t* pad, int64_t rows, int64_t cols,
+                          int k, bool f32, hipStream_t s, LaunchHook* hook);
+hipError_t unpad_rows_pairs(const uint64_t* pad, uint32_t* keys_out, uint32_t* vals_out, int64_t rows, int64_t cols,
+                            int k, bool f32, hipStream_t s, LaunchHook* hook);
 // How a row sort of `cols` keys runs (host only): *path 0 = sort_rows_tile
 // (*block_log2 = LR, *tile_log2 = LT, one KIND_TILE_SORT record), 1 = padded
 // blocks (*block_log2 = ceil_log2(cols), the passes of plan_passes(2^block_log2)).

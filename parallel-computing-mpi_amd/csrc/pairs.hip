@@ -30,10 +30,7 @@ constexpr int PAIRS_NT = 256, PAIRS_MAX_GRID = 2048;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
-// IEEE float bits <-> order-preserving u32 (ord_of_f64 / f64_of_ord on 32 bits).
-__device__ __forceinline__ uint32_t ord_of_f32(uint32_t b) { return (b >> 31) ? ~b : (b | 0x80000000u); }
-__device__ __forceinline__ uint32_t f32_of_ord(uint32_t o) { return (o >> 31) ? (o & 0x7FFFFFFFu) : ~o; }
-
+// K = ord_of_f32 / f32_of_ord (kernels.h) for f32 keys.
 template <bool F32>
 __device__ __forceinline__ uint64_t rec_of(uint32_t k, uint32_t v) {
     return (uint64_t)(F32 ? ord_of_f32(k) : k) << 32 | v;

@@ -19,6 +19,10 @@
 // the launchers take the vector kernel when it is 16-byte aligned and cols is a
 // multiple of the vector (every vector then lies inside one row), else element
 // accesses on the caller's side.
+//
+// The key-value rows (second pair of kernels) take the same path on u64
+// records: pad_rows_pairs zips keys and values into the padded buffer,
+// unpad_rows_pairs splits the sorted records into the two outputs.
 #include "kernels.h"
 
 namespace misort {
@@ -142,7 +146,122 @@ void launch_rows_copy(const void* src, void* dst, int64_t rows, int64_t cols, in
 #undef MISORT_ROWS_LAUNCH
 }
 
+// ---- key-value rows: the zip fused into the pad sweep, the unzip into the unpad
+//
+// The padded buffer holds the records K(key) << 32 | value of pairs.hip (K the
+// identity or ord_of_f32, applied to real keys only: the padding is the all-ones
+// record).  One 16-byte vector of the padded buffer = two records per lane and
+// trip; the caller's 32-bit arrays take 8-byte accesses (VEC: every array in use
+// 8-byte aligned and cols even, so both elements lie inside one row) or element
+// accesses.  vals null: the value of (r, c) is c.  keys null (unpad): values only.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+template <bool VEC, bool F32>
+__global__ __launch_bounds__(ROWS_NT) void k_pad_rows_pairs(const uint32_t* __restrict__ keys,
+                                                            const uint32_t* __restrict__ vals,
+                                                            uint64_t* __restrict__ padded, int64_t rows, int64_t cols,
+                                                            int k) {
+    typedef RowVec<uint64_t>::type vec_t;
+    const int64_t nq = (rows << k) / 2, cm = ((int64_t)1 << k) - 1;
+    const int64_t stride = (int64_t)gridDim.x * ROWS_NT;
+    for (int64_t q = (int64_t)blockIdx.x * ROWS_NT + threadIdx.x; q < nq; q += stride) {
+        const int64_t p = q * 2, r = p >> k, c = p & cm;
+        const int64_t off = r * cols + c;
+        vec_t x = {~(uint64_t)0, ~(uint64_t)0};
+        if constexpr (VEC) {
+            // cols even: both elements are real or neither
+            if (c < cols) {
+                const u32x2 kk = *reinterpret_cast<const u32x2*>(keys + off);
+                u32x2 vv = {(uint32_t)c, (uint32_t)c + 1u};
+                if (vals) vv = *reinterpret_cast<const u32x2*>(vals + off);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) x[j] = (uint64_t)(F32 ? ord_of_f32(kk[j]) : kk[j]) << 32 | vv[j];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (c + j < cols) {
+                    const uint32_t kk = keys[off + j], vv = vals ? vals[off + j] : (uint32_t)(c + j);
+                    x[j] = (uint64_t)(F32 ? ord_of_f32(kk) : kk) << 32 | vv;
+                }
+        }
+        reinterpret_cast<vec_t*>(padded)[q] = x;
+    }
+}
+
+template <bool VEC, bool F32>
+__global__ __launch_bounds__(ROWS_NT) void k_unpad_rows_pairs(const uint64_t* __restrict__ padded,
+                                                              uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                              int64_t rows, int64_t cols, int k) {
+    typedef RowVec<uint64_t>::type vec_t;
+    const int64_t nq = (rows << k) / 2, cm = ((int64_t)1 << k) - 1;
+    const int64_t stride = (int64_t)gridDim.x * ROWS_NT;
+    for (int64_t q = (int64_t)blockIdx.x * ROWS_NT + threadIdx.x; q < nq; q += stride) {
+        const int64_t p = q * 2, r = p >> k, c = p & cm;
+        if (c >= cols) continue;  // padding only: not read
+        const vec_t x = reinterpret_cast<const vec_t*>(padded)[q];
+        const int64_t off = r * cols + c;
+        u32x2 kk, vv;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t o = (uint32_t)(x[j] >> 32);
+            kk[j] = F32 ? f32_of_ord(o) : o;  // never stored where it is padding
+            vv[j] = (uint32_t)x[j];
+        }
+        if constexpr (VEC) {
+            if (keys) *reinterpret_cast<u32x2*>(keys + off) = kk;
+            *reinterpret_cast<u32x2*>(vals + off) = vv;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (c + j < cols) {
+                    if (keys) keys[off + j] = kk[j];
+                    vals[off + j] = vv[j];
+                }
+        }
+    }
+}
+
+bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }  // a null array is not accessed
+
+// k >= 1 keeps a block a whole number of 16-byte vectors
+bool rows_pairs_args_ok(const void* padded, int64_t rows, int64_t cols, int k) {
+    return padded && aligned16(padded) && k >= 1 && k <= 60 && cols <= ((int64_t)1 << k) &&
+           rows <= (INT64_MAX >> k) / 8;
+}
+
 }  // namespace
+
+hipError_t pad_rows_pairs(const uint32_t* keys_in, const uint32_t* vals_in, uint64_t* padded, int64_t rows,
+                          int64_t cols, int k, bool f32, hipStream_t s, LaunchHook* hook) {
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    if (!keys_in || !rows_pairs_args_ok(padded, rows, cols, k)) return hipErrorInvalidValue;
+    if (!vals_in && cols > ((int64_t)1 << 32)) return hipErrorInvalidValue;  // a 32-bit value holds 2^32 columns
+    const bool vec = aligned8(keys_in) && aligned8(vals_in) && cols % 2 == 0;
+    const double n = (double)rows * (double)cols;
+    OtherScope os(hook, n * (vals_in ? 8.0 : 4.0) + (double)rows * (double)((int64_t)1 << k) * 8.0, s);
+    const unsigned g = rows_grid((rows << k) / 2);
+    if (vec && f32) k_pad_rows_pairs<true, true><<<g, ROWS_NT, 0, s>>>(keys_in, vals_in, padded, rows, cols, k);
+    else if (vec) k_pad_rows_pairs<true, false><<<g, ROWS_NT, 0, s>>>(keys_in, vals_in, padded, rows, cols, k);
+    else if (f32) k_pad_rows_pairs<false, true><<<g, ROWS_NT, 0, s>>>(keys_in, vals_in, padded, rows, cols, k);
+    else k_pad_rows_pairs<false, false><<<g, ROWS_NT, 0, s>>>(keys_in, vals_in, padded, rows, cols, k);
+    return hipGetLastError();
+}
+
+hipError_t unpad_rows_pairs(const uint64_t* padded, uint32_t* keys_out, uint32_t* vals_out, int64_t rows,
+                            int64_t cols, int k, bool f32, hipStream_t s, LaunchHook* hook) {
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    if (!vals_out || !rows_pairs_args_ok(padded, rows, cols, k)) return hipErrorInvalidValue;
+    const bool vec = aligned8(keys_out) && aligned8(vals_out) && cols % 2 == 0;
+    const double n = (double)rows * (double)cols;
+    OtherScope os(hook, n * 8.0 + n * (keys_out ? 8.0 : 4.0), s);
+    const unsigned g = rows_grid((rows << k) / 2);
+    if (vec && f32) k_unpad_rows_pairs<true, true><<<g, ROWS_NT, 0, s>>>(padded, keys_out, vals_out, rows, cols, k);
+    else if (vec) k_unpad_rows_pairs<true, false><<<g, ROWS_NT, 0, s>>>(padded, keys_out, vals_out, rows, cols, k);
+    else if (f32) k_unpad_rows_pairs<false, true><<<g, ROWS_NT, 0, s>>>(padded, keys_out, vals_out, rows, cols, k);
+    else k_unpad_rows_pairs<false, false><<<g, ROWS_NT, 0, s>>>(padded, keys_out, vals_out, rows, cols, k);
+    return hipGetLastError();
+}
 
 hipError_t pad_rows(const void* in, void* padded, int64_t rows, int64_t cols, int k, int key_bytes, bool f64,
                     hipStream_t s, LaunchHook* hook) {

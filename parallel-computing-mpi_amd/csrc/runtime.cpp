@@ -2059,6 +2059,72 @@ int misort_local_sort_rows(misort_ctx* c, int dtype, const void* in, void* out, 
     return MISORT_OK;
 }
 
+// Key-value rows, 32-bit keys: the path of misort_local_sort_rows on u64 records
+// that exist in registers only (rows up to the u64 SORT tile: rows_pairs.hip) or
+// in the padded blocks (longer rows: the zip is the pad sweep, the unzip the
+// unpad sweep, rows.hip).  The dispatch is misort_rows_plan(cols, 8)'s.
+int misort_local_sort_rows_pairs(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in,
+                                 void* keys_out, void* vals_out, int64_t rows, int64_t cols, void* stream) {
+    if (!c) return fail(MISORT_E_INVALID, "null ctx");
+    if (!valid_pair_dtype(key_dtype))
+        return fail(MISORT_E_INVALID, "local_sort_rows_pairs takes MISORT_U32 or MISORT_F32 keys, got %d", key_dtype);
+    if (rows < 0 || cols < 0) return fail(MISORT_E_INVALID, "bad local_sort_rows_pairs arguments");
+    if (rows == 0 || cols == 0) return MISORT_OK;  // no array is looked at: empty ones may be null
+    if (!vals_in && cols > kIndexValues)
+        return fail(MISORT_E_INVALID, "argsort of rows of %lld keys: a 32-bit value holds 2^32 columns",
+                    (long long)cols);
+    int k = 0;  // ceil_log2(cols)
+    while (k < 62 && ((int64_t)1 << k) < cols) ++k;
+    // the padded blocks of 8-byte records of the long-row path must be addressable too
+    if (k >= 60 || rows > (INT64_MAX >> (k + 4)))
+        return fail(MISORT_E_INVALID, "local_sort_rows_pairs: %lld x %lld pairs are too many", (long long)rows,
+                    (long long)cols);
+    if (!keys_in || !vals_out) return fail(MISORT_E_INVALID, "bad local_sort_rows_pairs arguments");
+    const uint64_t bytes = (uint64_t)rows * (uint64_t)cols * 4;
+    // a tile or a pad sweep reads rows another workgroup may already have rewritten
+    const auto overlap = [bytes](const void* a, const void* b, bool same_ok) {
+        const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+        return a && b && !(same_ok && a0 == b0) && a0 < b0 + bytes && b0 < a0 + bytes;
+    };
+    if (overlap(keys_out, keys_in, true) || overlap(vals_out, vals_in, true))
+        return fail(MISORT_E_INVALID,
+                    "local_sort_rows_pairs: an output overlaps its input (only d_keys_out == d_keys_in and "
+                    "d_vals_out == d_vals_in are allowed)");
+    if (overlap(keys_out, vals_out, false) || overlap(keys_out, vals_in, false) || overlap(vals_out, keys_in, false) ||
+        overlap(keys_in, vals_in, false))
+        return fail(MISORT_E_INVALID, "local_sort_rows_pairs: the key and value arrays overlap");
+    hipStream_t s = pick(c, stream);
+    const bool f32 = key_dtype == MISORT_F32;
+    if (cols == 1) {
+        if (keys_out && keys_out != keys_in)
+            HIPCHK(hipMemcpyAsync(keys_out, keys_in, bytes, hipMemcpyDeviceToDevice, s));
+        if (!vals_in) HIPCHK(hipMemsetAsync(vals_out, 0, bytes, s));  // the index of a row's only column
+        else if (vals_out != vals_in) HIPCHK(hipMemcpyAsync(vals_out, vals_in, bytes, hipMemcpyDeviceToDevice, s));
+        return MISORT_OK;
+    }
+    hipError_t e;
+    if (k <= misort::tile_log2(8)) {
+        e = misort::sort_rows_pairs_tile((const uint32_t*)keys_in, (const uint32_t*)vals_in, (uint32_t*)keys_out,
+                                         (uint32_t*)vals_out, rows, cols, f32, s, hook(c));
+        if (e != hipSuccess) return fail(MISORT_E_HIP, "sort_rows_pairs_tile: %s", hipGetErrorString(e));
+        return MISORT_OK;
+    }
+    const int64_t n = rows << k;
+    int rc = c->rowpad.ensure((size_t)n * 8);
+    if (rc || (rc = c->pong.ensure((size_t)n * 8))) return rc;
+    // every input is read by the pad sweep, before the sort starts: outputs may be the inputs
+    e = misort::pad_rows_pairs((const uint32_t*)keys_in, (const uint32_t*)vals_in, (uint64_t*)c->rowpad.p, rows, cols, k,
+                               f32, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "pad_rows_pairs: %s", hipGetErrorString(e));
+    e = misort::local_sort<uint64_t>((const uint64_t*)c->rowpad.p, (uint64_t*)c->rowpad.p, n, false,
+                                     (uint64_t*)c->pong.p, s, hook(c), nullptr, false, k);
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "local_sort (row blocks of records): %s", hipGetErrorString(e));
+    e = misort::unpad_rows_pairs((const uint64_t*)c->rowpad.p, (uint32_t*)keys_out, (uint32_t*)vals_out, rows, cols, k,
+                                 f32, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "unpad_rows_pairs: %s", hipGetErrorString(e));
+    return MISORT_OK;
+}
+
 int misort_rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int* block_log2, int* passes,
                      int max_passes) {
     if (key_bytes != 4 && key_bytes != 8) return fail(MISORT_E_INVALID, "key_bytes must be 4 or 8");

@@ -81,6 +81,7 @@ def lib():
         "misort_local_sort_pairs64": ([vp, i32, vp, vp, i32, vp, vp, i64, vp], i32),
         "misort_parallel_sort_pairs": ([vp, i32, vp, vp, vp, vp, i64, i64, vp], i32),
         "misort_local_sort_rows": ([vp, i32, vp, vp, i64, i64, vp], i32),
+        "misort_local_sort_rows_pairs": ([vp, i32, vp, vp, vp, vp, i64, i64, vp], i32),
         "misort_rows_plan": ([i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32),
                               ctypes.POINTER(i32), i32], i32),
         "misort_merge_split": ([vp, i32, vp, i64, vp, i64, vp, i32, vp], i32),
@@ -480,6 +481,59 @@ class Context:
         out = self._pair_outputs(keys, None, None, out, n)
         _check(lib().misort_local_sort_pairs(self._h, dt, _ptr(keys), None, None, _ptr(out), n,
                                              self._stream(stream)))
+        return out
+
+    def _rows_pairs_shape(self, what, keys, values=None):
+        """(rows, cols) of the row-wise key-value sorts; the checks sort_rows makes."""
+        if keys.dim() < 1:
+            raise ValueError(f"{what} needs a tensor of rank >= 1")
+        if not keys.is_contiguous():
+            raise ValueError(f"{what} needs a contiguous tensor, got strides {tuple(keys.stride())}")
+        if values is not None and values.shape != keys.shape:
+            raise ValueError(f"values have shape {tuple(values.shape)}, the keys {tuple(keys.shape)}")
+        cols = keys.shape[-1]
+        return (keys.numel() // cols if cols else 0), cols
+
+    def sort_rows_pairs(self, keys, values=None, out_keys=None, out_values=None, stream=None):
+        """Key-value sort along the last dimension of contiguous tensors of any
+        rank >= 1: every row of ``shape[-1]`` pairs on its own, ascending by
+        (key, value), values compared unsigned: the order of sort_pairs, row by
+        row.  Keys are u32 (uint32/int32 storage) or float32 (total order of the
+        bit patterns: -0.0 before +0.0, negative NaNs first, positive NaNs last,
+        every key bit-exact); values are uint32/int32 storage of the keys'
+        shape.  ``values=None``: the value of a row's column c is c, so
+        ``out_values`` is the stable row-wise argsort (equal keys in column
+        order).  These are 32-bit indices where torch.sort returns int64.
+        The default outputs are NEW tensors and the inputs are left unchanged.
+        ``out_keys=keys`` and ``out_values=values`` sort in place; any other
+        overlap among the four tensors is a MisortError (code -1).  A
+        non-contiguous tensor, rank 0, a too-small output and a ``values`` of
+        another shape raise ValueError, wrong dtypes TypeError.  Returns
+        ``(out_keys, out_values)``."""
+        import torch
+        dt = _pair_key_dtype(keys)
+        _pair_values(values)
+        rows, cols = self._rows_pairs_shape("sort_rows_pairs", keys, values)
+        out_keys = torch.empty_like(keys) if out_keys is None else out_keys
+        out_values = self._pair_outputs(keys, values, out_keys, out_values, keys.numel())
+        _check(lib().misort_local_sort_rows_pairs(self._h, dt, _ptr(keys),
+                                                  _ptr(values) if values is not None else None, _ptr(out_keys),
+                                                  _ptr(out_values), rows, cols, self._stream(stream)))
+        return out_keys, out_values
+
+    def argsort_rows(self, keys, out=None, stream=None):
+        """The stable argsort along the last dimension of a contiguous tensor of
+        u32 or float32 keys (order as in sort_rows_pairs): ``out[..., j]`` is the
+        column of the row's j-th smallest key, equal keys in column order.  No
+        keys are written.  ``out`` is uint32/int32 storage (default: a new tensor
+        of the keys' shape, like u32 keys, int32 for float keys): 32-bit indices
+        where torch.argsort returns int64.  ``out`` must not overlap ``keys``
+        (MisortError, code -1)."""
+        dt = _pair_key_dtype(keys)
+        rows, cols = self._rows_pairs_shape("argsort_rows", keys)
+        out = self._pair_outputs(keys, None, None, out, keys.numel())
+        _check(lib().misort_local_sort_rows_pairs(self._h, dt, _ptr(keys), None, None, _ptr(out), rows, cols,
+                                                  self._stream(stream)))
         return out
 
     def sort_pairs64(self, keys, values, out_keys=None, out_values=None, n=None, stream=None):
