@@ -154,6 +154,15 @@ int misort_parallel_bitonic_sort(misort_ctx* ctx, int dtype, void* d_keys, int64
 /* Same, out of place: d_in is left unchanged, d_out receives the block
  * (d_in == d_out allowed).
  *
+ * Buffer contract (both forms).  The arrays need element alignment only (4
+ * bytes for u32, 8 for u64 / f64): the local sort of an array that is not
+ * 16-byte aligned goes through an aligned buffer of the context (see
+ * misort_local_sort); the stages after it (splitter samples, codec,
+ * merge-split, the f64 back-conversion) use scalar or alignment-tolerant
+ * accesses.  Exactly the loc_size keys of the block are written: with a
+ * capacity larger than the block, [loc_size, capacity) is left unchanged, as is
+ * everything outside the array; the out-of-place form leaves d_in unchanged.
+ *
  * Exchange volume: before each compare-split the partners swap splitter
  * samples (every S-th key, S = max(256, n/32768)) and both derive the same
  * lower bound of the merge-path crossing point, so each side sends only the
@@ -165,8 +174,25 @@ int misort_parallel_bitonic_sort(misort_ctx* ctx, int dtype, void* d_keys, int64
 int misort_parallel_bitonic_sort_oop(misort_ctx* ctx, int dtype, const void* d_in, void* d_out,
                                      int64_t loc_size, int64_t max_size, void* stream);
 
-/* psort.cc:175 local ascending sort of n keys on one GPU, d_in -> d_out
- * (d_in == d_out allowed). */
+/* psort.cc:175 local ascending sort of n keys on one GPU, d_in -> d_out.
+ *
+ * Buffer contract.  Exactly d_out[0, n) is written; d_in is left unchanged
+ * unless it is d_out.  d_in == d_out sorts in place; any other overlap of
+ * [d_in, d_in + n) and [d_out, d_out + n) is MISORT_E_INVALID, checked by
+ * address range before anything is launched (the passes of one sort read and
+ * write both arrays from different workgroups).
+ *
+ * Alignment: the element's (4 bytes for u32, 8 for u64 / f64).  The kernels of
+ * the sort that take 16-byte vector accesses through a caller's pointer are the
+ * SORT tile (loads of d_in, stores of its output), the 2-way merge pass (stores
+ * of full tiles) and the multi-way merge pass (stores of whole vectors; its
+ * bounds search also loads aligned lines, behind an alignment test).  Their
+ * loads of the runs they merge, the partition and fence kernels and the f64
+ * back-conversion sweep are scalar.  None of the vector kernels is handed a
+ * pointer that is not 16-byte aligned: such a d_out is sorted into a buffer the
+ * context keeps (n keys, grown on demand) and copied out on `stream`; such a
+ * d_in is first copied into the destination and sorted in place there.  16-byte
+ * aligned arrays launch exactly what they launched before this rule existed. */
 int misort_local_sort(misort_ctx* ctx, int dtype, const void* d_in, void* d_out, int64_t n,
                       void* stream);
 
@@ -324,7 +350,10 @@ int misort_rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int
  * shrinking hypercube sub-groups, RCCL send/recv with the partner, device merge.
  * Per-rank output sizes are data-dependent, exactly as in the reference:
  * *out_size receives this rank's count; MISORT_E_CAPACITY if it exceeds
- * out_capacity (the reference allocates (loc+1)*P).  d_in is not modified. */
+ * out_capacity (the reference allocates (loc+1)*P).  d_in is not modified and
+ * needs element alignment only (its local sort copies a d_in that is not
+ * 16-byte aligned into the context's run buffer first, as misort_local_sort
+ * does). */
 int misort_parallel_quick_sort(misort_ctx* ctx, int dtype, const void* d_in, int64_t loc_size,
                                void* d_out, int64_t out_capacity, int64_t* out_size, void* stream);
 
@@ -336,13 +365,19 @@ int misort_parallel_quick_sort(misort_ctx* ctx, int dtype, const void* d_in, int
  * (d_out receives loc_size keys: the globally sorted sequence in the callers'
  * block sizes); d_in != d_out.  The reference's versions are not well defined
  * (an uninitialised splitter at :318, MPI_INT used for doubles at :224/:269),
- * so parity is anchored on the sorted sequence, not on their per-rank sizes. */
+ * so parity is anchored on the sorted sequence, not on their per-rank sizes.
+ * d_in needs element alignment only (handled as in misort_parallel_quick_sort). */
 int misort_parallel_sample_sort(misort_ctx* ctx, int dtype, const void* d_in, void* d_out,
                                 int64_t loc_size, int64_t max_size, void* stream);
 
 /* Device half of compare_split_{max,min} (psort.cc:116-164) without the
  * exchange: d_out[0..nloc) = the nloc largest (keep_max=1) or smallest
- * (keep_max=0) keys of the sorted blocks local U recv, ascending. */
+ * (keep_max=0) keys of the sorted blocks local U recv, ascending.
+ * Exactly d_out[0, nloc) is written; d_local and d_recv are left unchanged.
+ * d_out must overlap neither of them (MISORT_E_INVALID, checked by address
+ * range: a merge tile reads keys another tile may already have written).  The
+ * arrays need element alignment only: the partition and merge kernels take
+ * scalar accesses. */
 int misort_merge_split(misort_ctx* ctx, int dtype, const void* d_local, int64_t nloc,
                        const void* d_recv, int64_t nrecv, void* d_out, int keep_max,
                        void* stream);
@@ -351,7 +386,9 @@ int misort_merge_split(misort_ctx* ctx, int dtype, const void* d_local, int64_t 
  * d_block): the path a hypercube stage takes when the partner's bracket k is
  * small (k <= nblock / MISORT_TAIL_DIV, default 8): only the end of the block
  * that the nrecv received keys reach is rewritten, staged through the context's
- * work buffer.  d_recv must not overlap d_block (MISORT_E_INVALID).  Exposed
+ * work buffer.  d_recv must not overlap d_block (MISORT_E_INVALID).  Nothing
+ * outside d_block[0, nblock) is written and d_recv is left unchanged; the
+ * arrays need element alignment only (scalar accesses).  Exposed
  * so the path is testable on its own (extension; the reference merges the
  * whole block every stage). */
 int misort_merge_split_tail(misort_ctx* ctx, int dtype, void* d_block, int64_t nblock,
@@ -359,7 +396,10 @@ int misort_merge_split_tail(misort_ctx* ctx, int dtype, void* d_block, int64_t n
 
 /* psort.cc:497-520 check_sort: local descents of this rank's block plus the
  * boundary descent against rank-1's last key, summed over the communicator.
- * Synchronous; *errors is valid on every rank. */
+ * Synchronous; *errors is valid on every rank.  d_keys is only read and needs
+ * element alignment only (the counting kernel takes scalar loads); every
+ * position i with d_keys[i] > d_keys[i+1] counts exactly once (f64: compared as
+ * doubles, so a NaN on either side is no descent). */
 int misort_check_sort(misort_ctx* ctx, int dtype, const void* d_keys, int64_t n,
                       int64_t* errors, void* stream);
 

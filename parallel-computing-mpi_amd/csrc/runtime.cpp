@@ -778,6 +778,7 @@ struct misort_ctx {
     DevBuf recs;  // key-value sort: the (key << 32 | value) records, 8 bytes per pair
     DevBuf recs2;  // 64-bit keys: the second sort's records (recs holds the first's until the end)
     DevBuf rowpad;  // row sort of long rows: every row padded to a 2^k-key block
+    DevBuf bounce;  // local sort of a caller's array that is not 16-byte aligned (local_sort_any)
     DevBuf qa, qb, qcnt;  // quick sort: current run, merge target, exchanged counts
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -894,6 +895,37 @@ int do_local_sort(misort_ctx* c, int dtype, const void* in, void* out, int64_t n
         e = misort::local_sort<uint64_t>((const uint64_t*)in, (uint64_t*)out, n, ord_in, (uint64_t*)c->pong.p, s,
                                          hook(c), io, ord_out);
     if (e != hipSuccess) return fail(MISORT_E_HIP, "local_sort: %s", hipGetErrorString(e));
+    return MISORT_OK;
+}
+
+// do_local_sort for a caller's arrays, which need element alignment only.
+// The SORT tile loads `in` and stores its output as 16-byte vectors, and the
+// merge passes (k_runs_merge's full tiles, mergek_chunk) store 16-byte vectors
+// to `out` whenever the plan's parity lands a pass there: none of them may see
+// a pointer that is not 16-byte aligned.  Such an `out` is sorted into the
+// context's bounce buffer and copied out on the stream; such an `in` is first
+// copied into the destination (then aligned) and sorted in place there.
+// Aligned arrays, and the context's own buffers of host staging (io), take
+// do_local_sort as it is: the pointer test is all this adds.
+int local_sort_any(misort_ctx* c, int dtype, const void* in, void* out, int64_t n, bool ord_in, hipStream_t s,
+                   const misort::StageIO* io = nullptr, bool ord_out = false) {
+    const bool in_ok = ((uintptr_t)in & 15) == 0, out_ok = ((uintptr_t)out & 15) == 0;
+    if ((in_ok && out_ok) || io || n <= 0) return do_local_sort(c, dtype, in, out, n, ord_in, s, io, ord_out);
+    const size_t bytes = (size_t)n * key_bytes(dtype);
+    void* dst = out;
+    if (!out_ok) {
+        const int rc = c->bounce.ensure(std::max<size_t>(16, bytes));
+        if (rc) return rc;
+        dst = c->bounce.p;
+    }
+    const void* src = in;
+    if (!in_ok) {
+        HIPCHK(hipMemcpyAsync(dst, in, bytes, hipMemcpyDeviceToDevice, s));
+        src = dst;
+    }
+    const int rc = do_local_sort(c, dtype, src, dst, n, ord_in, s, nullptr, ord_out);
+    if (rc) return rc;
+    if (dst != out) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToDevice, s));
     return MISORT_OK;
 }
 
@@ -1214,7 +1246,7 @@ int parallel_sort(misort_ctx* c, int dtype, const void* in, void* out, int64_t l
     }
     // no compare-split after the local sort: its last pass writes f64 bits
     bool ord_done = f64 && nst == 0 && !chunk_out;
-    if ((rc = do_local_sort(c, dtype, in, cur, loc, f64, s, io ? &lio : nullptr, ord_done))) return rc;
+    if ((rc = local_sort_any(c, dtype, in, cur, loc, f64, s, io ? &lio : nullptr, ord_done))) return rc;
     if (chunk_out && chunked) return MISORT_OK;  // after_last owned the f64 back-conversion
     if (chunk_out) {
         // a last pass that is not chunked (a multi-way pass): the caller copies
@@ -1442,7 +1474,7 @@ int parallel_quick(misort_ctx* c, int dtype, const void* in, int64_t loc, void* 
     int rc;
     if ((rc = c->qa.ensure(std::max<size_t>(16, (size_t)loc * w)))) return rc;
     if ((rc = c->qcnt.ensure(64))) return rc;
-    if ((rc = do_local_sort(c, dtype, in, c->qa.p, loc, f64, s))) return rc;  // psort.cc:398
+    if ((rc = local_sort_any(c, dtype, in, c->qa.p, loc, f64, s))) return rc;  // psort.cc:398
     int64_t rs = loc;
     uint64_t stale0 = 0;  // result_buffer[0] as last written: the median of an empty rank (psort.cc:399)
     auto key_at = [&](int64_t i, uint64_t& v) -> int {  // one key of the current run, to the host
@@ -1527,7 +1559,7 @@ int parallel_sample(misort_ctx* c, int dtype, const void* in, void* out, int64_t
     const bool f64 = dtype == MISORT_F64;
     int rc;
     if ((rc = c->qa.ensure(std::max<size_t>(16, (size_t)loc * w)))) return rc;
-    if ((rc = do_local_sort(c, dtype, in, c->qa.p, loc, f64, s))) return rc;
+    if ((rc = local_sort_any(c, dtype, in, c->qa.p, loc, f64, s))) return rc;
     if (p == 1) {
         if (loc > 0) HIPCHK(hipMemcpyAsync(out, c->qa.p, (size_t)loc * w, hipMemcpyDeviceToDevice, s));
         if (f64) HIPCHK(misort::ord_to_f64((uint64_t*)out, loc, s));
@@ -1942,9 +1974,14 @@ int64_t misort_block_size(int64_t n, int p, int rank) {
 int misort_local_sort(misort_ctx* c, int dtype, const void* in, void* out, int64_t n, void* stream) {
     if (!c || !valid_dtype(dtype) || n < 0 || (n > 0 && (!in || !out)))
         return fail(MISORT_E_INVALID, "bad local_sort arguments");
+    // the passes of one sort read and write both arrays from different workgroups
+    const uint64_t bytes = (uint64_t)n * key_bytes(dtype);
+    const uintptr_t a0 = (uintptr_t)in, b0 = (uintptr_t)out;
+    if (a0 != b0 && a0 < b0 + bytes && b0 < a0 + bytes)
+        return fail(MISORT_E_INVALID, "local_sort: d_out overlaps d_in (only d_out == d_in is allowed)");
     hipStream_t s = pick(c, stream);
     // f64: mapped to ordered u64 by the first pass, back by the last
-    return do_local_sort(c, dtype, in, out, n, dtype == MISORT_F64, s, nullptr, dtype == MISORT_F64);
+    return local_sort_any(c, dtype, in, out, n, dtype == MISORT_F64, s, nullptr, dtype == MISORT_F64);
 }
 
 int misort_local_sort_pairs(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in, void* keys_out,
@@ -2211,6 +2248,14 @@ int misort_merge_split(misort_ctx* c, int dtype, const void* local, int64_t nloc
                        int64_t nrecv, void* out, int keep_max, void* stream) {
     if (!c || !valid_dtype(dtype) || nloc < 0 || nrecv < 0)
         return fail(MISORT_E_INVALID, "bad merge_split arguments");
+    // a merge tile reads keys of both blocks that another tile may already have written
+    const auto overlaps_out = [&](const void* a, int64_t na) {
+        const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)out;
+        const uint64_t kb = key_bytes(dtype);
+        return na > 0 && nloc > 0 && a0 < b0 + (uint64_t)nloc * kb && b0 < a0 + (uint64_t)na * kb;
+    };
+    if (overlaps_out(local, nloc) || overlaps_out(recv, nrecv))
+        return fail(MISORT_E_INVALID, "merge_split: d_out overlaps d_local or d_recv");
     hipStream_t s = pick(c, stream);
     if (dtype != MISORT_F64) return do_merge_split(c, dtype, local, nloc, recv, nrecv, out, keep_max, s);
     // f64: order-preserving copies of both blocks, merge, map back.

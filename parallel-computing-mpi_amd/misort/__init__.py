@@ -296,6 +296,22 @@ def _pair64_check(n, **tensors):
             raise ValueError(f"{name}: a contiguous tensor of at least {n} elements is needed, got {tuple(t.shape)}")
 
 
+def _keys_check(ref, n, **tensors):
+    """The checks sort_rows makes, for the keys-only entry points: every tensor
+    given has ``ref``'s dtype (TypeError), is contiguous and holds at least
+    ``n`` elements (ValueError).  None is skipped."""
+    if n < 0:
+        raise ValueError(f"negative element count {n}")
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if t.dtype != ref.dtype:
+            raise TypeError(f"{name} is {t.dtype}, the keys are {ref.dtype}")
+        if t.numel() < n or not t.is_contiguous():
+            raise ValueError(f"{name}: a contiguous tensor of at least {n} elements is needed, "
+                             f"got {tuple(t.shape)} with strides {tuple(t.stride())}")
+
+
 class Context:
     """One GPU (HIP device) = one reference MPI rank.
 
@@ -368,10 +384,17 @@ class Context:
                               stream=None):
         """psort.cc:167.  Sorts this rank's block `buffer[:loc_buf_size]` with the
         reference's hypercube schedule; returns the tensor holding the result
-        (``buffer`` itself, or ``out`` when given: input left unchanged)."""
+        (``buffer`` itself, or ``out`` when given: input left unchanged).
+        Exactly the ``loc_buf_size`` keys of the block are written: the rest of
+        a larger buffer, and everything around a view, stay as they were.  The
+        tensors need element alignment only (a view that starts anywhere in its
+        storage).  A non-contiguous tensor and one holding fewer than
+        ``loc_buf_size`` elements raise ValueError, an ``out`` of another dtype
+        TypeError."""
         loc = buffer.numel() if loc_buf_size is None else int(loc_buf_size)
         mx = 0 if max_size is None else int(max_size)  # 0: the largest block (collective)
         dt = _dtype_of(buffer)
+        _keys_check(buffer, loc, buffer=buffer, out=out)
         if out is None:
             _check(lib().misort_parallel_bitonic_sort(self._h, dt, _ptr(buffer), loc, mx,
                                                       self._stream(stream)))
@@ -383,9 +406,14 @@ class Context:
     def parallel_quick_sort(self, buffer, loc_buf_size=None, out=None, stream=None):
         """psort.cc:377 (the reference binary's shipped sort).  Returns
         ``(out, n)``: this rank's sorted keys are ``out[:n]``, n data-dependent.
-        ``out`` defaults to the reference's capacity, (loc+1)*P keys."""
+        ``out`` defaults to the reference's capacity, (loc+1)*P keys.  A
+        non-contiguous tensor and a ``buffer`` of fewer than ``loc_buf_size``
+        elements raise ValueError, an ``out`` of another dtype TypeError (an
+        ``out`` too small for the result is MisortError, code -6)."""
         import torch
         loc = buffer.numel() if loc_buf_size is None else int(loc_buf_size)
+        _keys_check(buffer, loc, buffer=buffer)
+        _keys_check(buffer, 0, out=out)
         if out is None:
             out = torch.empty((loc + 1) * self.numprocs, dtype=buffer.dtype, device=buffer.device)
         n = ctypes.c_int64()
@@ -396,19 +424,32 @@ class Context:
     def parallel_sample_sort(self, buffer, loc_buf_size=None, max_size=None, out=None, stream=None):
         """psort.cc:203-375 redesigned (RCCL all-to-all).  Same contract as
         parallel_bitonic_sort: the globally sorted keys in the reference block
-        layout, out of place (``out`` defaults to a new tensor)."""
+        layout, out of place (``out`` defaults to a new tensor).  A
+        non-contiguous tensor and one holding fewer than ``loc_buf_size``
+        elements raise ValueError, an ``out`` of another dtype TypeError."""
         import torch
         loc = buffer.numel() if loc_buf_size is None else int(loc_buf_size)
         mx = 0 if max_size is None else int(max_size)
         out = torch.empty_like(buffer) if out is None else out
+        _keys_check(buffer, loc, buffer=buffer, out=out)
         _check(lib().misort_parallel_sample_sort(self._h, _dtype_of(buffer), _ptr(buffer), _ptr(out), loc, mx,
                                                  self._stream(stream)))
         return out
 
     def local_sort(self, inp, out=None, n=None, stream=None):
-        """psort.cc:175 (std::sort of the local block) on the GPU."""
+        """psort.cc:175 (std::sort of the local block) on the GPU: ``out[:n]`` =
+        the first ``n`` keys of ``inp`` ascending (f64: -0.0 before +0.0,
+        negative NaNs first, positive NaNs last, every key bit-exact).  The
+        default sorts in place; with another ``out`` the input is left
+        unchanged.  Exactly ``n`` elements are written.  The tensors need
+        element alignment only (a view that starts anywhere in its storage).
+        ``out`` is ``inp`` itself or does not overlap it: any other overlap of
+        the two ``n``-key ranges is a MisortError (code -1).  A non-contiguous
+        tensor and one holding fewer than ``n`` elements raise ValueError, an
+        ``out`` of another dtype TypeError."""
         out = inp if out is None else out
         n = inp.numel() if n is None else int(n)
+        _keys_check(inp, n, inp=inp, out=out)
         _check(lib().misort_local_sort(self._h, _dtype_of(inp), _ptr(inp), _ptr(out), n,
                                        self._stream(stream)))
         return out
@@ -599,9 +640,17 @@ class Context:
     def compare_split(self, local, recv, keep_max, out=None, stream=None, in_place_tail=False):
         """Device half of psort.cc:116-164 (no exchange).  in_place_tail: the
         small-bracket path of the hypercube stages (misort_merge_split_tail) on a
-        copy of `local` in `out`."""
+        copy of `local` in `out` (``out`` may be ``local`` itself: in place).
+        Exactly ``local.numel()`` elements of ``out`` are written; ``local`` (unless
+        it is ``out``) and ``recv`` are left unchanged.  Without in_place_tail
+        ``out`` must overlap neither ``local`` nor ``recv`` (MisortError, code
+        -1).  The tensors need element alignment only.  A non-contiguous tensor
+        and an ``out`` of fewer than ``local.numel()`` elements raise ValueError,
+        a ``recv`` or ``out`` of another dtype TypeError."""
         import torch
         out = torch.empty_like(local) if out is None else out
+        _keys_check(local, local.numel(), local=local, out=out)
+        _keys_check(local, 0, recv=recv)
         if in_place_tail:
             if out.data_ptr() != local.data_ptr():
                 out[:local.numel()].copy_(local)  # on torch's current stream
@@ -620,8 +669,14 @@ class Context:
         return out
 
     def check_sort(self, local_numbers, local_size=None, stream=None):
-        """psort.cc:497-520: total error count over the communicator."""
+        """psort.cc:497-520: total error count over the communicator: every
+        position i < local_size - 1 with a[i] > a[i+1] counts once (f64 compared
+        as doubles: a NaN on either side is no descent), plus the descents
+        between consecutive ranks' blocks.  The tensor is only read and needs
+        element alignment only; a non-contiguous one, or one of fewer than
+        ``local_size`` elements, raises ValueError."""
         n = local_numbers.numel() if local_size is None else int(local_size)
+        _keys_check(local_numbers, n, local_numbers=local_numbers)
         err = ctypes.c_int64()
         _check(lib().misort_check_sort(self._h, _dtype_of(local_numbers), _ptr(local_numbers), n,
                                        ctypes.byref(err), self._stream(stream)))
