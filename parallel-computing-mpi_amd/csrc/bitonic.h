@@ -730,24 +730,6 @@ __global__ __launch_bounds__((TileGeo<K, LT>::NT), (TileGeo<K, LT>::WAVES_PER_EU
     }
 }
 
-[[maybe_unused]] int ceil_log2(int64_t n) {
-    int k = 0;
-    while (((int64_t)1 << k) < n) ++k;
-    return k;
-}
-
-struct HookScope {
-    LaunchHook* h;
-    Kind k;
-    hipStream_t s;
-    HookScope(LaunchHook* h_, Kind k_, double bytes, hipStream_t s_) : h(h_), k(k_), s(s_) {
-        if (h) h->before(k, bytes, s);
-    }
-    ~HookScope() {
-        if (h) h->after(k, s);
-    }
-};
-
 // fence/flk: see final_store (null: no fences).
 template <typename K, int LT, bool ORD>
 void launch_sort_tile(const K* in, K* out, int64_t n, hipStream_t s, void* fence = nullptr, int flk = 0,

@@ -65,6 +65,29 @@ struct LaunchHook {
     virtual ~LaunchHook() = default;
 };
 
+// The hook's record of kind k around the launches of a scope (null hook: nothing).
+struct HookScope {
+    LaunchHook* h;
+    Kind k;
+    hipStream_t s;
+    HookScope(LaunchHook* h_, Kind k_, double bytes, hipStream_t s_) : h(h_), k(k_), s(s_) {
+        if (h) h->before(k, bytes, s);
+    }
+    ~HookScope() {
+        if (h) h->after(k, s);
+    }
+};
+
+// Host helpers the launchers share.  A null pointer is aligned: it is not accessed.
+inline bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// The smallest k with 2^k >= n, capped at 62 (n may come from a caller: no shift past the sign bit).
+inline int ceil_log2(int64_t n) {
+    int k = 0;
+    while (k < 62 && ((int64_t)1 << k) < n) ++k;
+    return k;
+}
+
 // A kernel launch carrying timing events (either may be null), or a plain one.
 template <typename F, typename... Args>
 inline void launch_timed(F kernel, dim3 grid, dim3 block, uint32_t shmem, hipStream_t s, hipEvent_t start,
@@ -268,7 +291,8 @@ hipError_t emit64(const uint64_t* s2, const uint64_t* s1, const void* vals_in, i
 //                   for cols <= c < 2^k (K = ord_of_f64 for f64 keys);
 //   unpad_rows      out[r cols + c] = unK(pad[r << k | c]) for c < cols.
 // pad is 16-byte aligned, 2^k >= 16 bytes of keys; the caller's arrays need
-// element alignment only.  Records of KIND_OTHER, each counted as
+// element alignment only.  The two sweeps are one pair of kernels for keys and
+// for the pairs below (rows.hip; rows_io.h says what a slot reads and writes).  Records of KIND_OTHER, each counted as
 // (rows cols + rows 2^k) keys (unpad skips the vectors that hold padding only).
 template <typename K>
 hipError_t sort_rows_tile(const K* in, K* out, int64_t rows, int64_t cols, bool f64, hipStream_t s,

@@ -112,19 +112,6 @@ unsigned pairs_grid(int64_t n) {
     return (unsigned)(g < 1 ? 1 : g > PAIRS_MAX_GRID ? PAIRS_MAX_GRID : g);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-struct OtherScope {  // the launch's KIND_OTHER record
-    LaunchHook* h;
-    hipStream_t s;
-    OtherScope(LaunchHook* h_, double bytes, hipStream_t s_) : h(h_), s(s_) {
-        if (h) h->before(KIND_OTHER, bytes, s);
-    }
-    ~OtherScope() {
-        if (h) h->after(KIND_OTHER, s);
-    }
-};
-
 }  // namespace
 
 hipError_t zip_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t val_base, uint64_t* rec, int64_t n,
@@ -132,7 +119,7 @@ hipError_t zip_pairs(const uint32_t* keys, const uint32_t* vals, uint32_t val_ba
     if (n <= 0) return hipSuccess;
     if (!aligned16(rec)) return hipErrorInvalidValue;
     const bool vec = aligned16(keys) && aligned16(vals);  // a null vals is not read
-    OtherScope os(hook, (double)n * (vals ? 16.0 : 12.0), s);
+    HookScope os(hook, KIND_OTHER, (double)n * (vals ? 16.0 : 12.0), s);
     const unsigned g = pairs_grid(n);
     if (vec && f32) k_zip_pairs<true, true><<<g, PAIRS_NT, 0, s>>>(keys, vals, val_base, rec, n);
     else if (vec) k_zip_pairs<true, false><<<g, PAIRS_NT, 0, s>>>(keys, vals, val_base, rec, n);
@@ -146,7 +133,7 @@ hipError_t unzip_pairs(const uint64_t* rec, uint32_t* keys, uint32_t* vals, int6
     if (n <= 0) return hipSuccess;
     if (!aligned16(rec) || !vals) return hipErrorInvalidValue;
     const bool vec = aligned16(keys) && aligned16(vals);  // a null keys is not written
-    OtherScope os(hook, (double)n * (keys ? 16.0 : 12.0), s);
+    HookScope os(hook, KIND_OTHER, (double)n * (keys ? 16.0 : 12.0), s);
     const unsigned g = pairs_grid(n);
     if (vec && f32) k_unzip_pairs<true, true><<<g, PAIRS_NT, 0, s>>>(rec, keys, vals, n);
     else if (vec) k_unzip_pairs<true, false><<<g, PAIRS_NT, 0, s>>>(rec, keys, vals, n);
@@ -305,7 +292,7 @@ hipError_t zip_lo64(const uint64_t* keys, uint64_t* rec, int64_t n, bool f64, hi
     if (n <= 0) return hipSuccess;
     if (!aligned16(rec) || !keys || n > ((int64_t)1 << 32)) return hipErrorInvalidValue;
     const bool vec = aligned16(keys);
-    OtherScope os(hook, (double)n * 16.0, s);
+    HookScope os(hook, KIND_OTHER, (double)n * 16.0, s);
     const unsigned g = pairs64_grid(n);
     if (vec && f64) k_zip_lo<true, true><<<g, PAIRS_NT, 0, s>>>(keys, rec, n);
     else if (vec) k_zip_lo<true, false><<<g, PAIRS_NT, 0, s>>>(keys, rec, n);
@@ -319,7 +306,7 @@ hipError_t gather_hi64(const uint64_t* s1, const uint64_t* keys, uint64_t* rec, 
     if (n <= 0) return hipSuccess;
     if (!aligned16(s1) || !aligned16(rec) || s1 == rec || !keys || n > ((int64_t)1 << 32))
         return hipErrorInvalidValue;
-    OtherScope os(hook, (double)n * 24.0, s);
+    HookScope os(hook, KIND_OTHER, (double)n * 24.0, s);
     const unsigned g = pairs64_grid(n);
     if (f64) k_gather_hi<true><<<g, PAIRS_NT, 0, s>>>(s1, keys, rec, n);
     else k_gather_hi<false><<<g, PAIRS_NT, 0, s>>>(s1, keys, rec, n);
@@ -333,7 +320,7 @@ hipError_t emit64(const uint64_t* s2, const uint64_t* s1, const void* vals_in, i
     if (vals_in ? (val_bytes != 4 && val_bytes != 8) : val_bytes != 4) return hipErrorInvalidValue;
     const int vb = vals_in ? val_bytes : 0;
     const bool vec = aligned16(keys_out) && aligned16(vals_out);  // a null keys_out is not written
-    OtherScope os(hook, (double)n * (16.0 + (keys_out ? 8.0 : 0.0) + (vb ? 2.0 * vb : 4.0)), s);
+    HookScope os(hook, KIND_OTHER, (double)n * (16.0 + (keys_out ? 8.0 : 0.0) + (vb ? 2.0 * vb : 4.0)), s);
     const unsigned g = pairs64_grid(n);
     if (vec && f64) launch_emit<true, true>(vb, g, s, s2, s1, vals_in, keys_out, vals_out, n);
     else if (vec) launch_emit<true, false>(vb, g, s, s2, s1, vals_in, keys_out, vals_out, n);

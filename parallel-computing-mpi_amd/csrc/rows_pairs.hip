@@ -174,10 +174,6 @@ void launch_rows_pairs(const uint32_t* keys_in, const uint32_t* vals_in, uint32_
     }
 }
 
-// a null array is not accessed
-bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 hipError_t sort_rows_pairs_tile(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out,

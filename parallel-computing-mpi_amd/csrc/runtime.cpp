@@ -1433,6 +1433,50 @@ int unzip_pairs(misort_ctx* c, int key_dtype, void* keys, void* vals, int64_t n,
     return MISORT_OK;
 }
 
+// [a, a + a_bytes) and [b, b + b_bytes) share a byte; a null array overlaps nothing.
+bool ranges_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// ------------------------------------------------------------ row-wise sorts
+//
+// The shape checks of the row entry points (`entry`, sorting `what`): an error,
+// or MISORT_OK with *k = ceil_log2(cols), *k = -1 where nothing is to do (no
+// array is looked at then: empty ones may be null).
+int rows_shape(const char* entry, const char* what, int64_t rows, int64_t cols, int* k) {
+    *k = -1;
+    if (rows < 0 || cols < 0) return fail(MISORT_E_INVALID, "bad %s arguments", entry);
+    if (rows == 0 || cols == 0) return MISORT_OK;
+    const int cl = misort::ceil_log2(cols);
+    // the padded blocks of the long-row path (8-byte records at the most) must be addressable too
+    if (cl >= 60 || rows > (INT64_MAX >> (cl + 4)))
+        return fail(MISORT_E_INVALID, "%s: %lld x %lld %s are too many", entry, (long long)rows, (long long)cols, what);
+    *k = cl;
+    return MISORT_OK;
+}
+
+// The padded blocks of the long-row path: rows blocks of 2^k records of
+// key_bytes in rowpad, and the ping-pong buffer the sort below takes as scratch.
+int ensure_row_blocks(misort_ctx* c, int64_t rows, int k, size_t key_bytes) {
+    const size_t bytes = (size_t)(rows << k) * key_bytes;
+    const int rc = c->rowpad.ensure(bytes);
+    return rc ? rc : c->pong.ensure(bytes);
+}
+
+// Every block of rowpad sorted on its own, as plain u32 or u64: the sweeps
+// around it map the keys themselves (rows.hip).
+int sort_row_blocks(misort_ctx* c, int64_t rows, int k, size_t key_bytes, hipStream_t s, const char* what) {
+    const int64_t n = rows << k;
+    const hipError_t e =
+        key_bytes == 4 ? misort::local_sort<uint32_t>((const uint32_t*)c->rowpad.p, (uint32_t*)c->rowpad.p, n, false,
+                                                      (uint32_t*)c->pong.p, s, hook(c), nullptr, false, k)
+                       : misort::local_sort<uint64_t>((const uint64_t*)c->rowpad.p, (uint64_t*)c->rowpad.p, n, false,
+                                                      (uint64_t*)c->pong.p, s, hook(c), nullptr, false, k);
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "local_sort (%s): %s", what, hipGetErrorString(e));
+    return MISORT_OK;
+}
+
 // The pair sort over the communicator: the records go through parallel_sort
 // as MISORT_U64 keys, in place in the context's record buffer.  Every rank
 // must hold the same number of pairs: with unequal blocks the compare-split
@@ -1976,8 +2020,7 @@ int misort_local_sort(misort_ctx* c, int dtype, const void* in, void* out, int64
         return fail(MISORT_E_INVALID, "bad local_sort arguments");
     // the passes of one sort read and write both arrays from different workgroups
     const uint64_t bytes = (uint64_t)n * key_bytes(dtype);
-    const uintptr_t a0 = (uintptr_t)in, b0 = (uintptr_t)out;
-    if (a0 != b0 && a0 < b0 + bytes && b0 < a0 + bytes)
+    if (in != out && ranges_overlap(in, bytes, out, bytes))
         return fail(MISORT_E_INVALID, "local_sort: d_out overlaps d_in (only d_out == d_in is allowed)");
     hipStream_t s = pick(c, stream);
     // f64: mapped to ordered u64 by the first pass, back by the last
@@ -2017,13 +2060,10 @@ int misort_local_sort_pairs64(misort_ctx* c, int key_dtype, const void* keys_in,
         return fail(MISORT_E_INVALID, "no d_vals_in: the output is u32 indices, val_bytes must be 4, got %d",
                     val_bytes);
     // emit64 gathers from vals_in while it writes both outputs
-    const auto overlap = [n](const void* a, int aw, const void* b, int bw) {
-        const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-        return a && b && a0 < b0 + (uint64_t)n * bw && b0 < a0 + (uint64_t)n * aw;
-    };
-    if (overlap(vals_out, val_bytes, vals_in, val_bytes) || overlap(keys_out, 8, vals_in, val_bytes))
+    const uint64_t kb = (uint64_t)n * 8, vb = (uint64_t)n * val_bytes;
+    if (ranges_overlap(vals_out, vb, vals_in, vb) || ranges_overlap(keys_out, kb, vals_in, vb))
         return fail(MISORT_E_INVALID, "local_sort_pairs64: an output overlaps d_vals_in");
-    if (overlap(keys_out, 8, vals_out, val_bytes))
+    if (ranges_overlap(keys_out, kb, vals_out, vb))
         return fail(MISORT_E_INVALID, "local_sort_pairs64: d_keys_out overlaps d_vals_out");
     hipStream_t s = pick(c, stream);
     const size_t rec_bytes = std::max<size_t>(16, (size_t)n * sizeof(uint64_t));
@@ -2051,19 +2091,13 @@ int misort_local_sort_rows(misort_ctx* c, int dtype, const void* in, void* out, 
     if (!c) return fail(MISORT_E_INVALID, "null ctx");
     if (!valid_dtype(dtype))
         return fail(MISORT_E_INVALID, "local_sort_rows takes MISORT_U32, MISORT_U64 or MISORT_F64 keys, got %d", dtype);
-    if (rows < 0 || cols < 0) return fail(MISORT_E_INVALID, "bad local_sort_rows arguments");
-    if (rows == 0 || cols == 0) return MISORT_OK;  // no array is looked at: empty ones may be null
-    const size_t kb = key_bytes(dtype);
-    int k = 0;  // ceil_log2(cols)
-    while (k < 62 && ((int64_t)1 << k) < cols) ++k;
-    // the padded blocks of the long-row path must be addressable too
-    if (k >= 60 || rows > (INT64_MAX >> (k + 4)))
-        return fail(MISORT_E_INVALID, "local_sort_rows: %lld x %lld keys are too many", (long long)rows, (long long)cols);
+    int k, rc = rows_shape("local_sort_rows", "keys", rows, cols, &k);
+    if (rc || k < 0) return rc;
     if (!in || !out) return fail(MISORT_E_INVALID, "bad local_sort_rows arguments");
+    const size_t kb = key_bytes(dtype);
     const uint64_t bytes = (uint64_t)rows * (uint64_t)cols * kb;
-    const uintptr_t a0 = (uintptr_t)in, b0 = (uintptr_t)out;
     // a tile or a pad sweep reads rows another workgroup may already have rewritten
-    if (a0 != b0 && a0 < b0 + bytes && b0 < a0 + bytes)
+    if (in != out && ranges_overlap(in, bytes, out, bytes))
         return fail(MISORT_E_INVALID, "local_sort_rows: d_out overlaps d_in (only d_out == d_in is allowed)");
     hipStream_t s = pick(c, stream);
     const bool f64 = dtype == MISORT_F64;
@@ -2078,19 +2112,10 @@ int misort_local_sort_rows(misort_ctx* c, int dtype, const void* in, void* out, 
         if (e != hipSuccess) return fail(MISORT_E_HIP, "sort_rows_tile: %s", hipGetErrorString(e));
         return MISORT_OK;
     }
-    const int64_t n = rows << k;
-    int rc = c->rowpad.ensure((size_t)n * kb);
-    if (rc || (rc = c->pong.ensure((size_t)n * kb))) return rc;
+    if ((rc = ensure_row_blocks(c, rows, k, kb))) return rc;
     e = misort::pad_rows(in, c->rowpad.p, rows, cols, k, (int)kb, f64, s, hook(c));
     if (e != hipSuccess) return fail(MISORT_E_HIP, "pad_rows: %s", hipGetErrorString(e));
-    // plain u64 between the two kernels: they map f64 keys themselves
-    if (kb == 4)
-        e = misort::local_sort<uint32_t>((const uint32_t*)c->rowpad.p, (uint32_t*)c->rowpad.p, n, false,
-                                         (uint32_t*)c->pong.p, s, hook(c), nullptr, false, k);
-    else
-        e = misort::local_sort<uint64_t>((const uint64_t*)c->rowpad.p, (uint64_t*)c->rowpad.p, n, false,
-                                         (uint64_t*)c->pong.p, s, hook(c), nullptr, false, k);
-    if (e != hipSuccess) return fail(MISORT_E_HIP, "local_sort (row blocks): %s", hipGetErrorString(e));
+    if ((rc = sort_row_blocks(c, rows, k, kb, s, "row blocks"))) return rc;
     e = misort::unpad_rows(c->rowpad.p, out, rows, cols, k, (int)kb, f64, s, hook(c));
     if (e != hipSuccess) return fail(MISORT_E_HIP, "unpad_rows: %s", hipGetErrorString(e));
     return MISORT_OK;
@@ -2105,30 +2130,22 @@ int misort_local_sort_rows_pairs(misort_ctx* c, int key_dtype, const void* keys_
     if (!c) return fail(MISORT_E_INVALID, "null ctx");
     if (!valid_pair_dtype(key_dtype))
         return fail(MISORT_E_INVALID, "local_sort_rows_pairs takes MISORT_U32 or MISORT_F32 keys, got %d", key_dtype);
-    if (rows < 0 || cols < 0) return fail(MISORT_E_INVALID, "bad local_sort_rows_pairs arguments");
-    if (rows == 0 || cols == 0) return MISORT_OK;  // no array is looked at: empty ones may be null
-    if (!vals_in && cols > kIndexValues)
+    // (before the shape checks' "too many"; empty and negative shapes are theirs)
+    if (rows > 0 && !vals_in && cols > kIndexValues)
         return fail(MISORT_E_INVALID, "argsort of rows of %lld keys: a 32-bit value holds 2^32 columns",
                     (long long)cols);
-    int k = 0;  // ceil_log2(cols)
-    while (k < 62 && ((int64_t)1 << k) < cols) ++k;
-    // the padded blocks of 8-byte records of the long-row path must be addressable too
-    if (k >= 60 || rows > (INT64_MAX >> (k + 4)))
-        return fail(MISORT_E_INVALID, "local_sort_rows_pairs: %lld x %lld pairs are too many", (long long)rows,
-                    (long long)cols);
+    int k, rc = rows_shape("local_sort_rows_pairs", "pairs", rows, cols, &k);
+    if (rc || k < 0) return rc;
     if (!keys_in || !vals_out) return fail(MISORT_E_INVALID, "bad local_sort_rows_pairs arguments");
     const uint64_t bytes = (uint64_t)rows * (uint64_t)cols * 4;
     // a tile or a pad sweep reads rows another workgroup may already have rewritten
-    const auto overlap = [bytes](const void* a, const void* b, bool same_ok) {
-        const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-        return a && b && !(same_ok && a0 == b0) && a0 < b0 + bytes && b0 < a0 + bytes;
-    };
-    if (overlap(keys_out, keys_in, true) || overlap(vals_out, vals_in, true))
+    if ((keys_out != keys_in && ranges_overlap(keys_out, bytes, keys_in, bytes)) ||
+        (vals_out != vals_in && ranges_overlap(vals_out, bytes, vals_in, bytes)))
         return fail(MISORT_E_INVALID,
                     "local_sort_rows_pairs: an output overlaps its input (only d_keys_out == d_keys_in and "
                     "d_vals_out == d_vals_in are allowed)");
-    if (overlap(keys_out, vals_out, false) || overlap(keys_out, vals_in, false) || overlap(vals_out, keys_in, false) ||
-        overlap(keys_in, vals_in, false))
+    if (ranges_overlap(keys_out, bytes, vals_out, bytes) || ranges_overlap(keys_out, bytes, vals_in, bytes) ||
+        ranges_overlap(vals_out, bytes, keys_in, bytes) || ranges_overlap(keys_in, bytes, vals_in, bytes))
         return fail(MISORT_E_INVALID, "local_sort_rows_pairs: the key and value arrays overlap");
     hipStream_t s = pick(c, stream);
     const bool f32 = key_dtype == MISORT_F32;
@@ -2146,16 +2163,12 @@ int misort_local_sort_rows_pairs(misort_ctx* c, int key_dtype, const void* keys_
         if (e != hipSuccess) return fail(MISORT_E_HIP, "sort_rows_pairs_tile: %s", hipGetErrorString(e));
         return MISORT_OK;
     }
-    const int64_t n = rows << k;
-    int rc = c->rowpad.ensure((size_t)n * 8);
-    if (rc || (rc = c->pong.ensure((size_t)n * 8))) return rc;
+    if ((rc = ensure_row_blocks(c, rows, k, 8))) return rc;
     // every input is read by the pad sweep, before the sort starts: outputs may be the inputs
     e = misort::pad_rows_pairs((const uint32_t*)keys_in, (const uint32_t*)vals_in, (uint64_t*)c->rowpad.p, rows, cols, k,
                                f32, s, hook(c));
     if (e != hipSuccess) return fail(MISORT_E_HIP, "pad_rows_pairs: %s", hipGetErrorString(e));
-    e = misort::local_sort<uint64_t>((const uint64_t*)c->rowpad.p, (uint64_t*)c->rowpad.p, n, false,
-                                     (uint64_t*)c->pong.p, s, hook(c), nullptr, false, k);
-    if (e != hipSuccess) return fail(MISORT_E_HIP, "local_sort (row blocks of records): %s", hipGetErrorString(e));
+    if ((rc = sort_row_blocks(c, rows, k, 8, s, "row blocks of records"))) return rc;
     e = misort::unpad_rows_pairs((const uint64_t*)c->rowpad.p, (uint32_t*)keys_out, (uint32_t*)vals_out, rows, cols, k,
                                  f32, s, hook(c));
     if (e != hipSuccess) return fail(MISORT_E_HIP, "unpad_rows_pairs: %s", hipGetErrorString(e));

@@ -290,16 +290,19 @@ def _pair64_key_dtype(keys):
     raise TypeError(f"unsupported key dtype {keys.dtype} (sort_pairs64/argsort64 take u64/f64 keys)")
 
 
-def _pair64_check(n, **tensors):
+def _span_check(n, **tensors):
+    """Every tensor given is contiguous and holds at least ``n`` elements
+    (ValueError): the check of every local entry point.  None is skipped."""
     for name, t in tensors.items():
         if t is not None and (t.numel() < n or not t.is_contiguous()):
-            raise ValueError(f"{name}: a contiguous tensor of at least {n} elements is needed, got {tuple(t.shape)}")
+            raise ValueError(f"{name}: a contiguous tensor of at least {n} elements is needed, "
+                             f"got {tuple(t.shape)} with strides {tuple(t.stride())}")
 
 
 def _keys_check(ref, n, **tensors):
-    """The checks sort_rows makes, for the keys-only entry points: every tensor
-    given has ``ref``'s dtype (TypeError), is contiguous and holds at least
-    ``n`` elements (ValueError).  None is skipped."""
+    """The checks of the keys-only entry points, tensor by tensor: each one given
+    has ``ref``'s dtype (TypeError) and passes _span_check (ValueError).  None
+    is skipped."""
     if n < 0:
         raise ValueError(f"negative element count {n}")
     for name, t in tensors.items():
@@ -307,9 +310,7 @@ def _keys_check(ref, n, **tensors):
             continue
         if t.dtype != ref.dtype:
             raise TypeError(f"{name} is {t.dtype}, the keys are {ref.dtype}")
-        if t.numel() < n or not t.is_contiguous():
-            raise ValueError(f"{name}: a contiguous tensor of at least {n} elements is needed, "
-                             f"got {tuple(t.shape)} with strides {tuple(t.stride())}")
+        _span_check(n, **{name: t})
 
 
 class Context:
@@ -467,14 +468,8 @@ class Context:
         dt = _dtype_of(inp)
         if inp.dim() < 1:
             raise ValueError("sort_rows needs a tensor of rank >= 1")
-        if not inp.is_contiguous():
-            raise ValueError(f"sort_rows needs a contiguous tensor, got strides {tuple(inp.stride())}")
         out = torch.empty_like(inp) if out is None else out
-        if out.dtype != inp.dtype:
-            raise TypeError(f"out is {out.dtype}, the input is {inp.dtype}")
-        if out.numel() < inp.numel() or not out.is_contiguous():
-            raise ValueError(f"out: a contiguous tensor of at least {inp.numel()} elements is needed, "
-                             f"got {tuple(out.shape)}")
+        _keys_check(inp, inp.numel(), inp=inp, out=out)
         cols = inp.shape[-1]
         rows = inp.numel() // cols if cols else 0
         _check(lib().misort_local_sort_rows(self._h, dt, _ptr(inp), _ptr(out), rows, cols, self._stream(stream)))
@@ -489,9 +484,7 @@ class Context:
         _pair_values(out_values, "out_values")
         if out_keys is not None and out_keys.dtype != keys.dtype:
             raise TypeError(f"out_keys is {out_keys.dtype}, the keys are {keys.dtype}")
-        for t in (keys, values, out_keys, out_values):
-            if t is not None and (t.numel() < n or not t.is_contiguous()):
-                raise ValueError(f"a contiguous tensor of at least {n} elements is needed, got {tuple(t.shape)}")
+        _span_check(n, keys=keys, values=values, out_keys=out_keys, out_values=out_values)
         return out_values
 
     def sort_pairs(self, keys, values=None, out_keys=None, out_values=None, n=None, stream=None):
@@ -598,7 +591,7 @@ class Context:
             raise TypeError(f"out_keys is {out_keys.dtype}, the keys are {keys.dtype}")
         if out_values.dtype != values.dtype:
             raise TypeError(f"out_values is {out_values.dtype}, the values are {values.dtype}")
-        _pair64_check(n, keys=keys, values=values, out_keys=out_keys, out_values=out_values)
+        _span_check(n, keys=keys, values=values, out_keys=out_keys, out_values=out_values)
         _check(lib().misort_local_sort_pairs64(self._h, dt, _ptr(keys), _ptr(values), values.element_size(),
                                                _ptr(out_keys), _ptr(out_values), n, self._stream(stream)))
         return out_keys, out_values
@@ -614,7 +607,7 @@ class Context:
         n = keys.numel() if n is None else int(n)
         out = torch.empty_like(keys, dtype=torch.int32) if out is None else out
         _pair_values(out, "out")
-        _pair64_check(n, keys=keys, out=out)
+        _span_check(n, keys=keys, out=out)
         _check(lib().misort_local_sort_pairs64(self._h, dt, _ptr(keys), None, 4, None, _ptr(out), n,
                                                self._stream(stream)))
         return out

@@ -318,7 +318,9 @@ def test_element_aligned_views(ctx, cols):
     aliasing_case(ctx, 7, cols, 1, 9600 + cols)  # one element into the storage, odd cols
 
 
-@pytest.mark.parametrize("cols", [1000, 1002, 10000])
+# 4096: a row is a whole 2^12 block and a tile holds two, so three tiles take the 8-byte
+# kernel's unchecked non-temporal accesses and the last, one row, its bounds checks
+@pytest.mark.parametrize("cols", [1000, 1002, 4096, 10000])
 def test_eight_byte_aligned_views(ctx, cols):
     aliasing_case(ctx, 7, cols, 2, 9650 + cols)  # two elements in: 8-byte accesses at the most
 

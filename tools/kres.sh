@@ -1,5 +1,5 @@
 #!/bin/bash
-# Per-kernel VGPRs / spills / LDS / occupancy of kernels.hip (compile-time check).
+# Per-kernel VGPRs / spills / scratch / LDS / occupancy of kernels.hip, or of KRES_SRC (compile-time check).
 #   tools/kres.sh [filter-regex]
 HERE="$(cd "$(dirname "$0")/.." && pwd)"
 C="$HERE/parallel-computing-mpi_amd/csrc"
@@ -14,11 +14,12 @@ for line in sys.stdin:
     if m:
         name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
         cur = {"name": name}; rows.append(cur); continue
-    m = re.search(r"remark: +(VGPRs|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+    m = re.search(r"remark: +(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]): (\d+)", line)
     if m and cur is not None:
         cur[m.group(1).split()[0] + (" spill" if "Spill" in m.group(1) else "")] = int(m.group(2))
 for r in rows:
     if not flt.search(r["name"]): continue
     n = re.sub(r"misort::\(anonymous namespace\)::", "", r["name"]).split("(")[0]
-    print("%-60s vgpr=%s spill=%s lds=%s occ=%s" % (n, r.get("VGPRs"), r.get("VGPRs spill"), r.get("LDS"), r.get("Occupancy")))
+    print("%-60s vgpr=%s spill=%s sgpr_spill=%s scratch=%s lds=%s occ=%s" % (
+        n, r.get("VGPRs"), r.get("VGPRs spill"), r.get("SGPRs spill"), r.get("ScratchSize"), r.get("LDS"), r.get("Occupancy")))
 ' "$@"
