@@ -345,6 +345,64 @@ int misort_local_sort_rows_pairs(misort_ctx* ctx, int key_dtype,
 int misort_rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int* block_log2,
                      int* passes, int max_passes);
 
+/* ---- segmented sort (extension) ---------------------------------------------- */
+
+/* Sorts variable-length segments of one array, each ascending on its own.
+ * d_offsets is a DEVICE array of nseg + 1 int64 values; segment i is the keys
+ * [d_offsets[i], d_offsets[i+1]) of d_in.  Well formed means 0 <= d_offsets[0],
+ * d_offsets[i] <= d_offsets[i+1] and d_offsets[nseg] <= n; empty segments are
+ * allowed.  dtype MISORT_U32, MISORT_U64 or MISORT_F64 (MISORT_F32:
+ * MISORT_E_INVALID); f64 keys sort as misort_local_sort(MISORT_F64) sorts them:
+ * -0.0 before +0.0, negative NaNs first, positive NaNs last.  Every output key
+ * is bit-identical to an input key.
+ *
+ * Written range: exactly d_out[0, n).  With d_out != d_in the keys outside
+ * [d_offsets[0], d_offsets[nseg]) are copied from d_in, so d_out is a complete
+ * result and d_in is left unchanged; in place (d_out == d_in) those keys are not
+ * touched.  Any other overlap of the two n-key ranges, and any overlap of d_out
+ * with the nseg + 1 offsets, is MISORT_E_INVALID, checked by address range
+ * before anything is launched.  The key arrays need element alignment only
+ * (segments start anywhere: every access to them is an element access); the
+ * offsets need 8-byte alignment.  0 <= nseg <= 2^31 - 1.  n == 0 launches
+ * nothing and looks at no pointer; nseg == 0 launches no kernel and looks at no
+ * key pointer except for the copy of all n keys when d_out != d_in.
+ * MISORT_E_INVALID for a null context (checked first), negative sizes, and a
+ * null array that would be read or written.
+ *
+ * ONE HOST WAIT PER CALL.  A count kernel reads d_offsets[0 .. nseg] (nothing
+ * else), validates every segment, and counts segments and keys per class
+ * (misort_segment_class) into a small header; the host waits for it and reads
+ * the header once (with a communicator the wait is bounded as in
+ * misort_synchronize), so that every later launch is sized exactly: a second
+ * sweep writes each class's segment list, then one launch per non-empty class.
+ * Everything after the wait is asynchronous on `stream`.  Because of the wait
+ * the call CANNOT BE CAPTURED IN A GRAPH, and work queued on `stream` before it
+ * is waited for.  Malformed offsets are refused there: MISORT_E_INVALID, the
+ * message names the first malformed index i (the pair d_offsets[i],
+ * d_offsets[i+1]), before any kernel that touches a key is launched: d_out is
+ * unchanged.  A merge pass's rejected chunk (MISORT_E_INTERNAL) is reported by
+ * misort_synchronize, as for misort_local_sort.
+ *
+ * How: segments up to 2^misort_tile_log2 keys go through the row tile of
+ * misort_local_sort_rows, one launch per class LR = 5 .. tile_log2: a tile holds
+ * 2^(LT-LR) segments of lengths in (2^(LR-1), 2^LR] (LR = 5: 1 .. 32), one HBM
+ * read and one write per key, no scratch.  Longer segments go class by class,
+ * k = ceil_log2(length), through the padded blocks of the long rows: gathered
+ * into blocks of 2^k keys filled up with all-ones, sorted by the passes of a
+ * 2^k-key misort_local_sort, the first `length` keys of every block written
+ * back.  Scratch kept by the context: 4 bytes per segment plus a 2 KiB header,
+ * and for the long classes two buffers of max over k (count_k * 2^k) keys. */
+int misort_local_sort_segments(misort_ctx* ctx, int dtype, const void* d_in, void* d_out, int64_t n,
+                               const int64_t* d_offsets, int64_t nseg, void* stream);
+
+/* Host only, no device: the class of a segment of `len` keys of key_bytes (4 or
+ * 8).  -1 for len == 0 (nothing to sort; also the status of a negative len or a
+ * bad key_bytes); for 1 <= len <= 2^misort_tile_log2(key_bytes) the row tile's
+ * LR = max(ceil_log2(len), 5); for longer segments ceil_log2(len), the k of the
+ * padded blocks.  For every len >= 2 it is misort_rows_plan(len, key_bytes)'s
+ * path and block size.  The kernels classify with the same function. */
+int misort_segment_class(int64_t len, int key_bytes);
+
 /* psort.cc:377-490 parallel_quick_sort (the reference binary's shipped sort,
  * called at psort.cc:647-648): d rounds of median-of-medians pivoting over
  * shrinking hypercube sub-groups, RCCL send/recv with the partner, device merge.

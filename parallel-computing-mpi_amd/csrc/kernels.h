@@ -333,6 +333,35 @@ int rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int* block
 // (one lane's registers).
 constexpr int ROWS_LR_MIN = 5;
 
+// Segmented sort (segs.hip, segs_tile.h): segment i of a caller's array is
+// [off[i], off[i + 1]), off a device array of nseg + 1 int64; its class is
+// segment_class(len) of segs_class.h, which also lays out the header.
+//   seg_count       validates and classifies every segment into the zeroed
+//                   header hdr (SEG_H_WORDS 64-bit words); reads only off[0..nseg];
+//   seg_scatter     writes every non-empty segment's index into its class's
+//                   list: cursor[class] (64-bit words, the host's list bases) is
+//                   advanced; `listed` is the lists' total length;
+//   sort_segs_tile  one class lr <= tile_log2: the `count` segments of `list`,
+//                   2^(LT - lr) per LDS tile, levels 1..lr (in == out allowed).
+//                   One KIND_TILE_SORT record of 2 `keys` keys;
+//   pad_segs        one class k > tile_log2: pad[r << k | c] = K(in[begin + c])
+//                   for c < len of segment list[r], all-ones above;
+//   unpad_segs      out[begin + c] = unK(pad[r << k | c]) for c < len.
+// pad is 16-byte aligned; the caller's arrays need element alignment only.
+// Count, scatter, pad and unpad are records of KIND_OTHER with the bytes moved
+// (`keys`: the class's key total).
+hipError_t seg_count(const int64_t* off, int64_t nseg, int64_t n, int key_bytes, void* hdr, hipStream_t s,
+                     LaunchHook* hook);
+hipError_t seg_scatter(const int64_t* off, int64_t nseg, int key_bytes, void* cursor, uint32_t* lists,
+                       int64_t listed, hipStream_t s, LaunchHook* hook);
+template <typename K>
+hipError_t sort_segs_tile(const K* in, K* out, const int64_t* off, const uint32_t* list, int64_t count, int lr,
+                          int64_t keys, bool f64, hipStream_t s, LaunchHook* hook);
+hipError_t pad_segs(const void* in, const int64_t* off, const uint32_t* list, int64_t count, int64_t keys, void* pad,
+                    int k, int key_bytes, bool f64, hipStream_t s, LaunchHook* hook);
+hipError_t unpad_segs(const void* pad, void* out, const int64_t* off, const uint32_t* list, int64_t count,
+                      int64_t keys, int k, int key_bytes, bool f64, hipStream_t s, LaunchHook* hook);
+
 // Counter-based SplitMix64 keys for global indices [g0, g0+n) (bench/test input).
 hipError_t fill_splitmix_u32(uint32_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);
 hipError_t fill_splitmix_u64(uint64_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);

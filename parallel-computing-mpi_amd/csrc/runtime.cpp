@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "segs_class.h"
 
 namespace {
 
@@ -779,6 +780,7 @@ struct misort_ctx {
     DevBuf recs2;  // 64-bit keys: the second sort's records (recs holds the first's until the end)
     DevBuf rowpad;  // row sort of long rows: every row padded to a 2^k-key block
     DevBuf bounce;  // local sort of a caller's array that is not 16-byte aligned (local_sort_any)
+    DevBuf segs;  // segmented sort: the count kernel's header, then the class lists (segs_class.h)
     DevBuf qa, qb, qcnt;  // quick sort: current run, merge target, exchanged counts
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -2181,6 +2183,113 @@ int misort_rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int
     if (cols < 0 || !path || !tile_log2 || !block_log2) return fail(MISORT_E_INVALID, "bad rows_plan arguments");
     if (max_passes > 0 && !passes) return fail(MISORT_E_INVALID, "null passes");
     return misort::rows_plan(cols, key_bytes, path, tile_log2, block_log2, passes, max_passes < 0 ? 0 : max_passes);
+}
+
+// Segmented sort: segment i is [off[i], off[i + 1]).  A count kernel validates
+// and classifies the segments (segs_class.h); the host reads its header ONCE
+// (the call's only wait: the launches below are sized from it exactly), refuses
+// malformed offsets before any kernel touches a key, and turns the per-class
+// counts into the bases of the class lists, which a second sweep fills.  Then
+// one row-tile launch per non-empty class up to the largest SORT tile
+// (segs_tile.h), and for every longer class k, one at a time, the padded blocks
+// of the long rows: pad, the passes of a 2^k-key sort over the class's blocks,
+// unpad (segs.hip).
+int misort_local_sort_segments(misort_ctx* c, int dtype, const void* in, void* out, int64_t n,
+                               const int64_t* offsets, int64_t nseg, void* stream) {
+    if (!c) return fail(MISORT_E_INVALID, "null ctx");
+    if (!valid_dtype(dtype))
+        return fail(MISORT_E_INVALID, "local_sort_segments takes MISORT_U32, MISORT_U64 or MISORT_F64 keys, got %d",
+                    dtype);
+    if (n < 0 || nseg < 0 || nseg > 0x7FFFFFFFll)
+        return fail(MISORT_E_INVALID, "bad local_sort_segments arguments (0 <= n, 0 <= nseg <= 2^31 - 1)");
+    // the padded blocks of the long classes (under 2 n keys of 8 bytes at the most) must be addressable too
+    if (n > (INT64_MAX >> 5))
+        return fail(MISORT_E_INVALID, "local_sort_segments: %lld keys are too many", (long long)n);
+    const size_t kb = key_bytes(dtype);
+    const uint64_t bytes = (uint64_t)n * kb, off_bytes = ((uint64_t)nseg + 1) * 8;
+    // a tile or a pad sweep reads segments another workgroup may already have rewritten,
+    // and every kernel reads the offsets while d_out is written
+    if (in != out && ranges_overlap(in, bytes, out, bytes))
+        return fail(MISORT_E_INVALID, "local_sort_segments: d_out overlaps d_in (only d_out == d_in is allowed)");
+    if (nseg > 0 && ranges_overlap(out, bytes, offsets, off_bytes))
+        return fail(MISORT_E_INVALID, "local_sort_segments: d_out overlaps d_offsets");
+    if (n == 0) return MISORT_OK;  // no array is looked at: empty ones may be null
+    hipStream_t s = pick(c, stream);
+    const auto copy = [&](int64_t k0, int64_t k1) -> int {  // d_out[k0, k1) = d_in[k0, k1), out of place
+        if (in == out || k1 <= k0) return MISORT_OK;
+        HIPCHK(hipMemcpyAsync((char*)out + (size_t)k0 * kb, (const char*)in + (size_t)k0 * kb, (size_t)(k1 - k0) * kb,
+                              hipMemcpyDeviceToDevice, s));
+        return MISORT_OK;
+    };
+    if (nseg == 0) {
+        if (in != out && (!in || !out)) return fail(MISORT_E_INVALID, "bad local_sort_segments arguments");
+        return copy(0, n);
+    }
+    if (!in || !out || !offsets) return fail(MISORT_E_INVALID, "bad local_sort_segments arguments");
+    if ((uintptr_t)offsets & 7) return fail(MISORT_E_INVALID, "local_sort_segments: d_offsets is not 8-byte aligned");
+    if (((uintptr_t)in | (uintptr_t)out) & (kb - 1))
+        return fail(MISORT_E_INVALID, "local_sort_segments: a key array is not aligned to its element");
+
+    int rc = c->segs.ensure(misort::SEG_LIST_BYTES + (size_t)nseg * sizeof(uint32_t));
+    if (rc) return rc;
+    char* hdr = (char*)c->segs.p;
+    uint32_t* lists = (uint32_t*)(hdr + misort::SEG_LIST_BYTES);
+    HIPCHK(hipMemsetAsync(hdr, 0, misort::SEG_H_WORDS * 8, s));
+    hipError_t e = misort::seg_count(offsets, nseg, n, (int)kb, hdr, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::seg_count: %s", hipGetErrorString(e));
+    int64_t h[misort::SEG_H_WORDS];
+    if ((rc = fetch(c, s, {{h, hdr, misort::SEG_H_FETCH * 8}}))) return rc;  // the call's one host wait
+    if (h[misort::SEG_H_BAD] != 0)
+        return fail(MISORT_E_INVALID,
+                    "local_sort_segments: malformed offsets: %lld of %lld segments, the first at index %lld "
+                    "(0 <= offsets[i] <= offsets[i + 1] <= n = %lld is needed); nothing was written",
+                    (long long)h[misort::SEG_H_BAD], (long long)nseg, (long long)~h[misort::SEG_H_BAD_AT], (long long)n);
+    // the class lists, class after class; the long classes' blocks
+    const int lt = misort::seg_tile_log2((int)kb);
+    int64_t base[misort::SEG_CLASSES], listed = 0, blocks_max = 0;
+    for (int k = 0; k < misort::SEG_CLASSES; ++k) {
+        base[k] = listed;
+        listed += h[misort::SEG_H_COUNT + k];
+        if (k > lt && h[misort::SEG_H_COUNT + k] > 0) blocks_max = std::max(blocks_max, h[misort::SEG_H_COUNT + k] << k);
+    }
+    if (listed > nseg) return fail(MISORT_E_INTERNAL, "local_sort_segments: the count kernel listed too many segments");
+    if ((rc = copy(0, h[misort::SEG_H_FIRST])) || (rc = copy(h[misort::SEG_H_LAST], n))) return rc;
+    if (listed == 0) return MISORT_OK;  // every segment is empty
+    // (both scratch buffers before the first key kernel: growing one frees it, which waits for the device)
+    if (blocks_max > 0) {
+        if ((rc = c->rowpad.ensure((size_t)blocks_max * kb)) || (rc = c->pong.ensure((size_t)blocks_max * kb)))
+            return rc;
+    }
+    if ((rc = h2d(c, hdr + misort::SEG_H_CURSOR * 8, base, sizeof(base), s))) return rc;
+    e = misort::seg_scatter(offsets, nseg, (int)kb, hdr + misort::SEG_H_CURSOR * 8, lists, listed, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::seg_scatter: %s", hipGetErrorString(e));
+    const bool f64 = dtype == MISORT_F64;
+    for (int lr = misort::SEG_LR_MIN; lr <= lt; ++lr) {
+        const int64_t count = h[misort::SEG_H_COUNT + lr], keys = h[misort::SEG_H_KEYS + lr];
+        if (count == 0) continue;
+        e = kb == 4 ? misort::sort_segs_tile<uint32_t>((const uint32_t*)in, (uint32_t*)out, offsets, lists + base[lr], count, lr,
+                                               keys, false, s, hook(c))
+                    : misort::sort_segs_tile<uint64_t>((const uint64_t*)in, (uint64_t*)out, offsets, lists + base[lr], count, lr,
+                                               keys, f64, s, hook(c));
+        if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::sort_segs_tile (class %d): %s", lr, hipGetErrorString(e));
+    }
+    // a class's pad has read all its keys before its sort starts, its unpad writes only its own segments
+    for (int k = lt + 1; k < misort::SEG_CLASSES; ++k) {
+        const int64_t count = h[misort::SEG_H_COUNT + k], keys = h[misort::SEG_H_KEYS + k];
+        if (count == 0) continue;
+        e = misort::pad_segs(in, offsets, lists + base[k], count, keys, c->rowpad.p, k, (int)kb, f64, s, hook(c));
+        if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::pad_segs (class %d): %s", k, hipGetErrorString(e));
+        if ((rc = sort_row_blocks(c, count, k, kb, s, "segment blocks"))) return rc;
+        e = misort::unpad_segs(c->rowpad.p, out, offsets, lists + base[k], count, keys, k, (int)kb, f64, s, hook(c));
+        if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::unpad_segs (class %d): %s", k, hipGetErrorString(e));
+    }
+    return MISORT_OK;
+}
+
+int misort_segment_class(int64_t len, int key_bytes) {
+    if (key_bytes != 4 && key_bytes != 8) return fail(MISORT_E_INVALID, "key_bytes must be 4 or 8");
+    if (len < 0) return fail(MISORT_E_INVALID, "negative segment length");
+    return misort::segment_class(len, key_bytes);
 }
 
 int misort_parallel_sort_pairs(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in, void* keys_out,

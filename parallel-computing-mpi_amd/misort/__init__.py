@@ -20,6 +20,7 @@ __all__ = [
     "U32", "U64", "F64", "F32", "MisortError", "NotPowerOfTwo", "NativeLibraryMissing",
     "library_path", "lib", "Context", "Group", "block_sizes", "schedule", "tile_log2", "plan",
     "sample_indices", "exchange_count", "set_shared_gpu_env", "rows_plan",
+    "segment_class",
 ]
 
 U32, U64, F64 = 0, 1, 2
@@ -84,6 +85,8 @@ def lib():
         "misort_local_sort_rows_pairs": ([vp, i32, vp, vp, vp, vp, i64, i64, vp], i32),
         "misort_rows_plan": ([i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32),
                               ctypes.POINTER(i32), i32], i32),
+        "misort_local_sort_segments": ([vp, i32, vp, vp, i64, vp, i64, vp], i32),
+        "misort_segment_class": ([i64, i32], i32),
         "misort_merge_split": ([vp, i32, vp, i64, vp, i64, vp, i32, vp], i32),
         "misort_merge_split_tail": ([vp, i32, vp, i64, vp, i64, i32, vp], i32),
         "misort_parallel_quick_sort": ([vp, i32, vp, i64, vp, i64, ctypes.POINTER(i64), vp], i32),
@@ -199,6 +202,16 @@ def rows_plan(cols, key_bytes=4):
     return {"path": ("tile", "blocks")[path.value], "tile_log2": tile.value, "block_log2": block.value,
             "passes": [(KIND_NAMES[buf[4 * i]], buf[4 * i + 1], buf[4 * i + 2], bool(buf[4 * i + 3]))
                        for i in range(np_)]}
+
+
+def segment_class(len, key_bytes=4):
+    """The class Context.sort_segments sorts a segment of ``len`` keys in: -1 for
+    an empty one; up to 2^tile_log2(key_bytes) keys the row tile's block_log2,
+    max(ceil_log2(len), 5); for longer ones ceil_log2(len), the block of the
+    padded path.  For len >= 2 it is rows_plan(len, key_bytes)'s path and block."""
+    if len < 0 or key_bytes not in (4, 8):
+        raise ValueError(f"segment_class({len}, {key_bytes}): len >= 0 and key_bytes 4 or 8 are needed")
+    return int(lib().misort_segment_class(len, key_bytes))
 
 
 class Group:
@@ -473,6 +486,43 @@ class Context:
         cols = inp.shape[-1]
         rows = inp.numel() // cols if cols else 0
         _check(lib().misort_local_sort_rows(self._h, dt, _ptr(inp), _ptr(out), rows, cols, self._stream(stream)))
+        return out
+
+    def sort_segments(self, inp, offsets, out=None, stream=None):
+        """Sorts variable-length segments of the 1-D contiguous key tensor ``inp``
+        (u32/u64/f64 keys as in local_sort), each ascending on its own:
+        segment i is ``inp[offsets[i]:offsets[i + 1]]``.  ``offsets`` is a 1-D
+        contiguous int64 tensor on ``inp``'s device with at least one element,
+        non-decreasing, within [0, inp.numel()]; empty segments are allowed.
+        The default is a NEW tensor (keys outside the segments are copied, the
+        input is left unchanged); ``out=inp`` sorts in place and leaves the
+        keys outside the segments alone.  Returns ``out``.
+
+        The call waits once on the host for a kernel that validates and counts
+        the segments (so it cannot be captured in a graph); malformed offsets
+        are a MisortError (code -1) naming the first bad index, and nothing is
+        written then.  Any overlap of ``out`` with ``inp`` other than
+        ``out is inp``, or with ``offsets``, is a MisortError (code -1).  Wrong
+        dtypes raise TypeError; wrong shapes, non-contiguous tensors, a
+        too-small ``out`` and an ``offsets`` on another device ValueError."""
+        import torch
+        dt = _dtype_of(inp)
+        if offsets.dtype != torch.int64:
+            raise TypeError(f"offsets is {offsets.dtype}, int64 is needed")
+        if inp.dim() != 1:
+            raise ValueError(f"sort_segments needs a 1-D key tensor, got {tuple(inp.shape)}")
+        if offsets.dim() != 1 or offsets.numel() < 1 or not offsets.is_contiguous():
+            raise ValueError("offsets: a contiguous 1-D tensor of at least one element is needed, "
+                             f"got {tuple(offsets.shape)} with strides {tuple(offsets.stride())}")
+        if offsets.device != inp.device:
+            raise ValueError(f"offsets is on {offsets.device}, the keys are on {inp.device}")
+        out = torch.empty_like(inp) if out is None else out
+        n = inp.numel()
+        _keys_check(inp, n, inp=inp, out=out)
+        if out.device != inp.device:
+            raise ValueError(f"out is on {out.device}, the keys are on {inp.device}")
+        _check(lib().misort_local_sort_segments(self._h, dt, _ptr(inp), _ptr(out), n, _ptr(offsets),
+                                                offsets.numel() - 1, self._stream(stream)))
         return out
 
     # ---- key-value sort ----------------------------------------------------------
