@@ -13,7 +13,8 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import misort  # noqa: E402
-from guard_bands import TAIL, assert_guards, canary_for, guarded, kmap, kunmap  # noqa: E402
+from guard_bands import TAIL, assert_guards, canary_for, guarded  # noqa: E402
+from segment_layouts import FAMILIES, make, offsets_of, rand, want  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -49,65 +50,6 @@ def bits(t):
     if t.element_size() == 8:
         return t.view(torch.int64).cpu().numpy().view(np.uint64)
     return t.view(torch.int32).cpu().numpy().view(np.uint32)
-
-
-def offsets_of(lens, first=0):
-    return np.concatenate([[first], first + np.cumsum(np.asarray(lens, dtype=np.int64))]).astype(np.int64)
-
-
-def seg_ids(offs):
-    lens = np.diff(offs)
-    ids = np.repeat(np.arange(lens.size, dtype=np.int64), lens)
-    pos = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(offs[:-1] - offs[0], lens)
-    return ids, pos, np.repeat(lens, lens)
-
-
-def want(k, offs, dt):
-    """The oracle on bit patterns: k with every segment sorted (f64: by kmap)."""
-    out = k.copy()
-    a, b = int(offs[0]), int(offs[-1])
-    ids, _, _ = seg_ids(offs)
-    body = k[a:b]
-    o = kmap(body.view(np.float64)) if dt == np.float64 else body
-    order = np.lexsort((o, ids))
-    out[a:b] = body[order]
-    return out
-
-
-def rand(rng, n, u):
-    return rng.integers(0, np.iinfo(u).max, size=n, dtype=u, endpoint=True)
-
-
-def fam_sentinels(rng, ids, pos, ln, u):
-    k = rand(rng, ids.size, u)
-    k[pos % 3 == 0] = np.iinfo(u).max  # a third of each segment: the padding value
-    return k
-
-
-def fam_opposed(rng, ids, pos, ln, u):
-    """Every key of segment i lies above every key of segment i + 1."""
-    top = int(ids.max()) + 1 if ids.size else 1
-    assert top < (1 << 11)
-    return ((top - ids) * (1 << 20) + rng.integers(0, 1 << 20, ids.size)).astype(u)
-
-
-FAMILIES = {
-    "random": lambda rng, ids, pos, ln, u: rand(rng, ids.size, u),
-    "dups": lambda rng, ids, pos, ln, u: ((ids * 4 + rng.integers(0, 4, ids.size)).astype(u) * u(0x01000193)),
-    "sentinels": fam_sentinels,
-    "opposed": fam_opposed,
-    "ascending": lambda rng, ids, pos, ln, u: (pos * 3 + ids * 7919).astype(u),
-    "descending": lambda rng, ids, pos, ln, u: ((ln - pos) * 3 + ids * 7919).astype(u),
-}
-
-
-def make(family, seed, offs, n, u):
-    """n keys (bit patterns): the family inside [offs[0], offs[-1]), random outside."""
-    rng = np.random.default_rng(seed)
-    k = rand(rng, n, u)
-    ids, pos, ln = seg_ids(offs)
-    k[int(offs[0]):int(offs[-1])] = FAMILIES[family](rng, ids, pos, ln, u)
-    return k
 
 
 def check(ctx, k, offs, dt, what="", in_place=False):
