@@ -41,6 +41,13 @@
 #include "kernels.h"
 #include "lds_merge.h"
 
+// Build switch (tools/build_variant.sh): MISORT_TILE_DIRECT 0 = the SORT tiles
+// transpose their loaded keys through LDS before the register levels (see the
+// SORT tile engine below).
+#ifndef MISORT_TILE_DIRECT
+#define MISORT_TILE_DIRECT 1
+#endif
+
 namespace misort {
 
 // Planner knobs (environment, read once per process, kernels.hip):
@@ -167,8 +174,20 @@ __device__ __forceinline__ void store_vec(K* __restrict__ p, int64_t i0, int64_t
 // register buffer, so HBM streams through the LDS work.  Key v of a tile is
 // tile*2^LT + v.
 //
-// Register slots: lane t loads LOADS = 32/V vectors, slot k = virtual keys
+// Register slots: lane t loads LOADS = 32/V vectors, slot k = the tile's keys
 // (k*NT + t)*V .. +V-1 (coalesced 16-byte loads and stores).
+//
+// Levels 1..5 sort 32 keys per lane in registers: the 32 keys the lane loaded,
+// as they are.  The input is unsorted and the keys carry no payload, so which
+// 32 keys of the tile a lane sorts first cannot change the output: the lane's
+// sorted keys DEFINE the virtual keys 32 t .. 32 t + 31 of the network, and its
+// write of them to s[pad(32 t) + c] is the tile's first LDS access.  (Up to
+// round 8, MISORT_TILE_DIRECT=0, the tiles first transposed the loaded keys
+// through LDS -- 32 writes at pad(e + j), a workgroup barrier, 32 reads of the
+// lane's consecutive virtual keys -- so every wave waited for the whole
+// workgroup's loads; measured in profiles/r09/tile_lds.)  A partial last
+// tile's padding is then the MAX keys of the LOADED positions past n; an f64
+// tile maps exactly the loaded positions below n to ordered u64.
 //
 // LDS layout: key v at word v + v/32.  The padding keeps every phase's
 // 32-lane accesses on distinct banks, and since v + v/32 is additive over
@@ -684,12 +703,38 @@ __global__ __launch_bounds__((TileGeo<K, LT>::NT), (TileGeo<K, LT>::WAVES_PER_EU
     K pre[G::LOADS][G::V];
     int64_t tile = blockIdx.x;
     if (tile >= ntiles) return;
-    // ORD (f64 keys): mapped to ordered u64 once each lane holds its 32
-    // consecutive keys, not on load (converting each loaded vector made every
-    // LDS write wait for its own load: 4.27 -> 4.74 ms per 2^29 SORT pass)
+    // ORD (f64 keys): mapped to ordered u64 once each lane holds its 32 keys
+    // for the register levels, not on load (converting each loaded vector
+    // made every LDS write wait for its own load: 4.27 -> 4.74 ms per 2^29
+    // SORT pass)
     tile_fetch<K, LT, false>(pre, in, tile, n, t);
     for (; tile < ntiles; tile += gridDim.x) {
         const bool full = ((tile + 1) << LT) <= n;
+        const int64_t nxt = tile + gridDim.x;
+#if MISORT_TILE_DIRECT
+        {   // levels 1..5 on the 32 keys the lane loaded, which become the
+            // virtual keys 32 t .. 32 t + 31 (see the engine's comment)
+            K v[32];
+            const int a0 = pad(t << 5);
+#pragma unroll
+            for (int c = 0; c < 32; ++c) v[c] = pre[c / G::V][c % G::V];
+            if constexpr (ORD) {
+                // the loaded keys past n stay MAX (sentinels, never stored)
+#pragma unroll
+                for (int c = 0; c < 32; ++c) {
+                    const int64_t gi = (tile << LT) + place<K, LT>(c / G::V, t) + c % G::V;
+                    if (full || gi < n) v[c] = (K)ord_of_f64((uint64_t)v[c]);
+                }
+            }
+            sort32_regs<K>(v);
+            // the tile's first LDS access: the previous tile's final_store
+            // reads lie before the barrier that ends the loop body
+#pragma unroll
+            for (int c = 0; c < 32; ++c) s[a0 + c] = v[c];
+        }
+        // after the register levels: pre is free again
+        if (PERSIST && nxt < ntiles) tile_fetch<K, LT, false>(pre, in, nxt, n, t);
+#else
         // registers -> LDS
 #pragma unroll
         for (int k = 0; k < G::LOADS; ++k) {
@@ -698,7 +743,6 @@ __global__ __launch_bounds__((TileGeo<K, LT>::NT), (TileGeo<K, LT>::WAVES_PER_EU
             for (int j = 0; j < G::V; ++j) s[pad(e + j)] = pre[k][j];
         }
         __syncthreads();
-        const int64_t nxt = tile + gridDim.x;
         if (PERSIST && nxt < ntiles) tile_fetch<K, LT, false>(pre, in, nxt, n, t);
         {   // levels 1..5: window [0,5), 32 consecutive keys per lane
             K v[32];
@@ -716,6 +760,7 @@ __global__ __launch_bounds__((TileGeo<K, LT>::NT), (TileGeo<K, LT>::WAVES_PER_EU
 #pragma unroll
             for (int c = 0; c < 32; ++c) s[a0 + c] = v[c];
         }
+#endif
         wave_sync();  // level 6 stays inside the wave
         if constexpr (MF > 0) {
             sort_levels_w<K, 6, MF - 1>(s, t);
@@ -812,6 +857,7 @@ __global__ __launch_bounds__(1 << (LT - 5), LT == 14 ? 4 : 1) void k_sort_u32(
         int t = threadIdx.x;
         asm volatile("" : "+v"(t));
         const int a0 = pad(t << 5);
+#if !MISORT_TILE_DIRECT
 #pragma unroll
         for (int k = 0; k < G::LOADS; ++k) {
             const int e = place<K, LT>(k, t);
@@ -820,13 +866,23 @@ __global__ __launch_bounds__(1 << (LT - 5), LT == 14 ? 4 : 1) void k_sort_u32(
         }
         if constexpr (MERGE) lds_barrier();  // no wait for the previous tile's stores
         else __syncthreads();
+#endif
         {
             uint32_t x[32];
+#if MISORT_TILE_DIRECT
+            // the 32 keys the lane loaded become the virtual keys 32 t ..
+            // 32 t + 31; the write below is the tile's first LDS access (the
+            // previous tile's final_store reads lie before the barrier that
+            // ends the loop body)
+#pragma unroll
+            for (int c = 0; c < 32; ++c) x[c] = pre[c / G::V][c % G::V];
+#else
 #pragma unroll
             for (int c = 0; c < 32; ++c) x[c] = s[a0 + c];
+#endif
             sort32_regs<uint32_t>(x);
             wave_levels<6, WL>(x, t & 63);
-            // each lane rewrites only the keys it read: no barrier before, and the
+            // each lane writes only its own 32 slots: no barrier before, and the
             // next phase (level WL+1 <= 11) stays inside the wave
 #pragma unroll
             for (int c = 0; c < 32; ++c) s[a0 + c] = x[c];

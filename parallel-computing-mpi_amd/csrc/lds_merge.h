@@ -8,6 +8,14 @@
 #include "corank_seed.h"
 #include "kernels.h"
 
+// Build switch (tools/build_variant.sh): MISORT_FOLD_SENTINELS 0 = every merge
+// level writes its sentinels and zero words in a loop of their own after the
+// outputs (lds_merge_levels); 1 (default) = the lanes past a pair's end store
+// them, in the shapes where that measured faster; 2 = in every shape.
+#ifndef MISORT_FOLD_SENTINELS
+#define MISORT_FOLD_SENTINELS 1
+#endif
+
 namespace misort {
 namespace {
 
@@ -307,7 +315,20 @@ __device__ __forceinline__ void lds_merge_prologue(KEY* s, const int (&st)[S::K]
 // Level lv writes pair p's output at qp[p] (a multiple of QA past the
 // previous pair's sentinels) with G sentinels after it; the last level's
 // outputs stay in registers: lane tid holds outputs [tid * IT, tid * IT + IT)
-// of the merged sequence as r[0, IT).  S (a shape): K, LKS, NT, IT, G, QA,
+// of the merged sequence as r[0, IT).
+// Where FOLD holds (below: the uniform shapes and those without zero words)
+// the sentinels are the outputs of the lanes past a pair's end: pairs start at
+// lane boundaries (QA = IT), so the lanes from a pair's end to the next pair's
+// start tile that gap (G .. 2 IT words), their chains start at the end of both
+// sequences and output MAX alone, and they store it like any output; after the
+// last pair the lanes up to G words past its end do (a wave that lies wholly
+// past the outputs skips its chains and stores MAX registers).  ZW: the lane
+// whose slots end at the next pair's start stores 0 in its last word.
+// Elsewhere (the u32 k_mergek; every shape up to round 8 and with
+// MISORT_FOLD_SENTINELS=0) those lanes store nothing and a loop over P * G
+// words writes the sentinels, a division and a select chain over the pair ends
+// per word, and a second select chain the zero words (profiles/r09/tile_lds).
+// S (a shape): K, LKS, NT, IT, G, QA,
 // CH (chain: 0 one key per read, 1 two), MAXR (bound on a pair's shorter
 // sequence), optionally ZW (shape_zw: G - 1 MAX sentinels and a zero word
 // after each sequence) and UNI (shape_uni).  MODE (probes,
@@ -322,6 +343,18 @@ __device__ __forceinline__ void lds_merge_levels(KEY* s, int (&st)[S::K], int (&
     constexpr int K = S::K, LK = S::LKS, NT = S::NT, IT = S::IT, G = S::G, CH = S::CH;
     constexpr bool ZW = shape_zw<S>::v;
     constexpr bool EQ = shape_uni<S>::v;  // a uniform shape's pairs: LA == LB
+    // the level's sentinels and zero words come from the lanes between the
+    // pairs (below); they tile those gaps because pairs start at lane
+    // boundaries, and every level layout ends within the NT lanes' slots (the
+    // shapes assert keys + (K / 2) (G + QA) <= NT * IT)
+    // Measured (profiles/r09/tile_lds): the u32 SORT tile -35 us per 2^30 pass and
+    // the u64 k_mergek -17 us per 2^29 pass; the u32 k_mergek +20 us per 2^30
+    // pass -- with zero words and per-pair geometry the lane that stores the
+    // zero word is found by a compare per pair in every wave, no cheaper than
+    // the sentinel loop that only the first waves run -- so those shapes
+    // keep the loop unless MISORT_FOLD_SENTINELS is 2.
+    constexpr bool FOLD = MISORT_FOLD_SENTINELS >= 2 || (MISORT_FOLD_SENTINELS == 1 && (shape_uni<S>::v || !ZW));
+    static_assert(!FOLD || (S::QA == IT && G > IT), "folded sentinels: lane-aligned pairs, a gap of more than one lane");
     bool full = false;  // the wave's sticky fallback to the full co-rank search (co_rank_run)
     static_assert(CH == 0 || CH == 1, "one- or two-key chains");
     // a two-key chain reads at most IT keys past a sequence (the one-key chain
@@ -347,6 +380,8 @@ __device__ __forceinline__ void lds_merge_levels(KEY* s, int (&st)[S::K], int (&
         const corank::Level L = corank::level(maxr, maxt, (int)sizeof(KEY));  // scalar work
         // the lane's pair: the last one starting at or before pos
         int A0 = st[0], LA = ln[0], B0 = st[1], LB = ln[1], Q = 0, LP = lp[0];
+        // FOLD, ZW, a uniform shape: the start of the pair after the lane's (-1: none)
+        [[maybe_unused]] int NQ = -1;
         if (P > 1) {
             if constexpr (shape_uni<S>::v) {
                 const int SL = uni_stride<S>(lv), SI = uni_in_stride<S>(lv), L0 = uni_len<S>(lv);
@@ -358,6 +393,8 @@ __device__ __forceinline__ void lds_merge_levels(KEY* s, int (&st)[S::K], int (&
                 LB = L0;
                 Q = pi * SL;
                 LP = 2 * L0;
+                // (a lane past the last pair's stride never ends at NQ)
+                if constexpr (FOLD && ZW) NQ = Q + SL < P * SL ? Q + SL : -1;
             } else {
 #pragma unroll
                 for (int p = 1; p < K / 2; ++p) {
@@ -385,12 +422,31 @@ __device__ __forceinline__ void lds_merge_levels(KEY* s, int (&st)[S::K], int (&
                 merge_chain<KEY, IT, S::MAXR, ZW, EQ>(s, A0, LA, B0, LB, pos - Q, L, full, r);
             else
                 merge_chain_blk<KEY, IT, S::MAXR, ZW, EQ>(s, A0, LA, B0, LB, pos - Q, L, full, r);
+        } else if (FOLD && lv < LK && wpos < end + G) {
+            // a wave past the outputs whose first lanes still write sentinels
+#pragma unroll
+            for (int j = 0; j < IT; ++j) r[j] = MAXK;
         }
         lds_barrier();
         if (lv < LK) {
             // a lane's outputs past its pair's end are MAX (the chain ran into
-            // the sentinels), the value the sentinel stores write there too
-            if (pos < Q + LP) {
+            // the sentinels).  FOLD: the lanes between a pair's end and the
+            // next pair's start (after the last pair: up to G words past its
+            // end) hold MAX alone and store it as the level's sentinels; the
+            // one whose slots end at the next pair's start stores the zero
+            // word (ZW) in its last.  Else the sentinel stores below write them.
+            if constexpr (FOLD && ZW) {
+                bool z = pos + IT == NQ;
+                if constexpr (!shape_uni<S>::v) {
+                    // against the (uniform) pair starts, here and not in the
+                    // selects above: no register held across the chain
+#pragma unroll
+                    for (int p = 1; p < K / 2; ++p)
+                        if (p < P) z |= pos + IT == qp[p];
+                }
+                r[IT - 1] = z ? (KEY)0 : r[IT - 1];
+            }
+            if (FOLD ? pos < end + G : pos < Q + LP) {
                 if constexpr (IT % 2) {
 #pragma unroll
                     for (int k = 0; k < IT; ++k) s[pos + k] = r[k];
@@ -400,27 +456,29 @@ __device__ __forceinline__ void lds_merge_levels(KEY* s, int (&st)[S::K], int (&
                         *reinterpret_cast<kvec2<KEY>*>(s + pos + j) = kvec2<KEY>{r[j], r[j + 1]};
                 }
             }
-            // ZW: G - 1 MAX words after each output and a zero word below each
-            // pair's output but the first (the next level's A sequences start
-            // there; the one below the first was written once)
-            constexpr int GW = ZW ? G - 1 : G;
-            for (int x = tid; x < P * GW; x += NT) {
-                const int p = x / GW;
-                int e = 0;
-#pragma unroll
-                for (int q = 0; q < K / 2; ++q)
-                    if (q < P) e = p == q ? qp[q] + lp[q] : e;
-                s[e + (x - p * GW)] = MAXK;
-            }
-            if constexpr (ZW) {
-                // the last wave's lanes 1 .. P-1 (its lanes past the sentinel loop's)
-                const int zl = tid - (NT - 64);
-                if (zl >= 1 && zl < P) {
+            if constexpr (!FOLD) {
+                // ZW: G - 1 MAX words after each output and a zero word below each
+                // pair's output but the first (the next level's A sequences start
+                // there; the one below the first was written once)
+                constexpr int GW = ZW ? G - 1 : G;
+                for (int x = tid; x < P * GW; x += NT) {
+                    const int p = x / GW;
                     int e = 0;
 #pragma unroll
-                    for (int q = 1; q < K / 2; ++q)
-                        if (q < P) e = zl == q ? qp[q] : e;
-                    s[e - 1] = (KEY)0;
+                    for (int q = 0; q < K / 2; ++q)
+                        if (q < P) e = p == q ? qp[q] + lp[q] : e;
+                    s[e + (x - p * GW)] = MAXK;
+                }
+                if constexpr (ZW) {
+                    // the last wave's lanes 1 .. P-1 (its lanes past the sentinel loop's)
+                    const int zl = tid - (NT - 64);
+                    if (zl >= 1 && zl < P) {
+                        int e = 0;
+#pragma unroll
+                        for (int q = 1; q < K / 2; ++q)
+                            if (q < P) e = zl == q ? qp[q] : e;
+                        s[e - 1] = (KEY)0;
+                    }
                 }
             }
             lds_barrier();

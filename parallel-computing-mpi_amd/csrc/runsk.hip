@@ -1037,7 +1037,15 @@ __device__ __forceinline__ void mergek_run(KEY* tile, const KEY* __restrict__ sr
                                            int lwn, int lkn) {
     typedef Shape<KEY, LK> S;
     KEY* s = tile + PAD;
-    const int tid = threadIdx.x;
+    int tid = threadIdx.x;
+#if MISORT_FOLD_SENTINELS >= 2
+    // lane id through an opaque copy: the capacity split's loop over halves
+    // recomputes the per-lane addresses every chunk instead of hoisting them
+    // (with the sentinels folded in every shape the u32 16-way kernel, at its
+    // 80 VGPRs, spilled three hoisted ones to scratch; profiles/r09/tile_lds)
+    asm volatile("" : "+v"(tid));
+    __builtin_assume(tid >= 0 && tid < S::NT);
+#endif
     {
         // loads: lane slot j = row j * NR + part, lane offset lt; the wave's
         // table entries first (scalar registers), then all its loads

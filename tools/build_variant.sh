@@ -7,10 +7,16 @@ HERE="$(cd "$(dirname "$0")/.." && pwd)"
 C="$HERE/parallel-computing-mpi_amd/csrc"; L="$HERE/parallel-computing-mpi_amd/lib"; O="$L/variants/$1"
 mkdir -p "$O"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -I$HERE/include -I$C $2"
-for src in sort_u32 sort_u64 kernels runs runsk runsk_fg6 codec; do
+# every kernel source of libmisort.so (csrc/Makefile); runtime.o is the default build's
+SRCS="kernels sort_u32 sort_u64 codec pairs rows rows_u32 rows_u64 rows_pairs segs segs_u32 segs_u64 runs runsk runsk_fg6"
+pids=""
+for src in $SRCS; do
   /opt/rocm/bin/hipcc $F -c "$C/$src.hip" -o "$O/$src.o" &
+  pids="$pids $!"
 done
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$L/variants/libmisort_$1.so" "$O/kernels.o" "$O/sort_u32.o" \
-  "$O/sort_u64.o" "$O/codec.o" "$O/runs.o" "$O/runsk.o" "$O/runsk_fg6.o" "$L/runtime.o" -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+for p in $pids; do wait "$p"; done
+OBJS=""
+for src in $SRCS; do OBJS="$OBJS $O/$src.o"; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$L/variants/libmisort_$1.so" $OBJS "$L/runtime.o" \
+  -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 rm -rf "$O"

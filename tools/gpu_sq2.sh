@@ -15,7 +15,7 @@ O = os.path.join(os.environ["GRAFT_REPO_ROOT"], "gpurun_out", os.environ.get("OU
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
 for f in glob.glob(f"{O}/p*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
-        key = re.sub(r"\(.*", "", r["Kernel_Name"]).replace("void misort::(anonymous namespace)::", "")
+        key = re.sub(r"\(.*", "", r["Kernel_Name"].replace("void misort::(anonymous namespace)::", ""))
         acc[key][r["Counter_Name"]] += float(r["Counter_Value"]); n[(key, r["Counter_Name"])] += 1
 for k, c in sorted(acc.items()):
     d = {x: v / max(1, n[(k, x)]) for x, v in c.items()}
