@@ -14,11 +14,19 @@
  * RCCL over xGMI, and keys live in HBM.  All entry points are extern "C", take
  * plain pointers and sizes, return 0 on success or a negative MISORT_E_* code
  * (message via misort_last_error()), and never throw.  A context is not
- * thread-safe; use one per thread/GPU.
+ * thread-safe; use one per thread/GPU.  Nor is it stream-safe: a context's
+ * scratch buffers are shared by all its calls, whatever stream they are given.
+ * Calls on one stream need nothing, they run in the order they were made.
+ * Calls on different streams of one context must be ordered by the caller, with
+ * an event or a wait, so that one has finished on the device before the next
+ * starts; unordered calls on two streams of one context are undefined.
  *
  * Device pointers are HIP device addresses on the context's GPU.  `stream` is a
  * hipStream_t (NULL = the context's own stream); calls are asynchronous on it
- * unless stated otherwise.
+ * unless stated otherwise: a call may be queued behind work that has not run
+ * yet, every step of it (kernels, copies, conversions) is ordered on `stream`,
+ * and what follows it on `stream` sees its result.  A call that grows one of
+ * the context's scratch buffers (the first of its size) may wait for the device.
  */
 #ifndef MISORT_H
 #define MISORT_H
@@ -257,7 +265,9 @@ int misort_local_sort_pairs64(misort_ctx* ctx, int key_dtype, const void* d_keys
  * records would be duplicated or lost: tolerable for bare keys as the
  * reference's documented defect, not for payloads).  d_vals_in == NULL: the
  * value is the global index rank*loc + i (nranks*loc <= 2^32).  max_size as in
- * misort_parallel_bitonic_sort. */
+ * misort_parallel_bitonic_sort.  Not asynchronous: at P > 1 the host waits on
+ * `stream` as misort_parallel_bitonic_sort does, and a caller must not rely on
+ * its returning early at P = 1. */
 int misort_parallel_sort_pairs(misort_ctx* ctx, int key_dtype, const void* d_keys_in, const void* d_vals_in,
                                void* d_keys_out, void* d_vals_out, int64_t loc_size, int64_t max_size,
                                void* stream);
@@ -411,7 +421,9 @@ int misort_segment_class(int64_t len, int key_bytes);
  * out_capacity (the reference allocates (loc+1)*P).  d_in is not modified and
  * needs element alignment only (its local sort copies a d_in that is not
  * 16-byte aligned into the context's run buffer first, as misort_local_sort
- * does). */
+ * does).  Not asynchronous: at P > 1 the host waits on `stream` several times
+ * in every round (the median, the pivot's position and the partner's count are
+ * read back), and a caller must not rely on its returning early at P = 1. */
 int misort_parallel_quick_sort(misort_ctx* ctx, int dtype, const void* d_in, int64_t loc_size,
                                void* d_out, int64_t out_capacity, int64_t* out_size, void* stream);
 
@@ -424,7 +436,10 @@ int misort_parallel_quick_sort(misort_ctx* ctx, int dtype, const void* d_in, int
  * block sizes); d_in != d_out.  The reference's versions are not well defined
  * (an uninitialised splitter at :318, MPI_INT used for doubles at :224/:269),
  * so parity is anchored on the sorted sequence, not on their per-rank sizes.
- * d_in needs element alignment only (handled as in misort_parallel_quick_sort). */
+ * d_in needs element alignment only (handled as in misort_parallel_quick_sort).
+ * Not asynchronous: at P > 1 the host waits on `stream` (block sizes, samples
+ * and the all-to-all-v counts are read back), and a caller must not rely on its
+ * returning early at P = 1. */
 int misort_parallel_sample_sort(misort_ctx* ctx, int dtype, const void* d_in, void* d_out,
                                 int64_t loc_size, int64_t max_size, void* stream);
 

@@ -331,6 +331,13 @@ class Context:
 
     ``dtype`` of a tensor selects the key type: uint32/int32 storage = u32 keys,
     uint64/int64 storage = u64 keys (compared unsigned), float64 = f64 keys.
+
+    ``stream=None`` is torch's current stream of the context's device; calls
+    are asynchronous on their stream unless their docstring says otherwise.  A
+    context's scratch buffers are shared by all its calls: calls on one stream
+    need nothing, calls on different streams of one context must be ordered by
+    the caller (an event or a wait); unordered ones are undefined.  A context
+    is not thread-safe either: one per thread.
     """
 
     def __init__(self, device=0):
@@ -683,7 +690,8 @@ class Context:
     def compare_split(self, local, recv, keep_max, out=None, stream=None, in_place_tail=False):
         """Device half of psort.cc:116-164 (no exchange).  in_place_tail: the
         small-bracket path of the hypercube stages (misort_merge_split_tail) on a
-        copy of `local` in `out` (``out`` may be ``local`` itself: in place).
+        copy of `local` in `out` (``out`` may be ``local`` itself: in place; the
+        copy runs on ``stream`` like the merge, behind whatever is queued there).
         Exactly ``local.numel()`` elements of ``out`` are written; ``local`` (unless
         it is ``out``) and ``recv`` are left unchanged.  Without in_place_tail
         ``out`` must overlap neither ``local`` nor ``recv`` (MisortError, code
@@ -696,13 +704,14 @@ class Context:
         _keys_check(local, 0, recv=recv)
         if in_place_tail:
             if out.data_ptr() != local.data_ptr():
-                out[:local.numel()].copy_(local)  # on torch's current stream
+                # the copy is a step of the call: on `stream`, behind what is queued
+                # there (which may still be writing `local`) and before the merge
                 cur = torch.cuda.current_stream(local.device)
                 if stream is not None and int(stream) != cur.cuda_stream:
-                    # the merge on `stream` starts after the copy
-                    done = torch.cuda.Event()
-                    done.record(cur)
-                    torch.cuda.ExternalStream(int(stream), device=local.device).wait_event(done)
+                    with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=local.device)):
+                        out[:local.numel()].copy_(local)
+                else:
+                    out[:local.numel()].copy_(local)
             _check(lib().misort_merge_split_tail(self._h, _dtype_of(local), _ptr(out), local.numel(),
                                                  _ptr(recv), recv.numel(), int(keep_max), self._stream(stream)))
             return out

@@ -9,6 +9,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import misort  # noqa: E402
+from sort_oracles import argsort_oracle, pairs_oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -40,24 +41,6 @@ def bits(t):
     """The 32-bit patterns of a device tensor (u32 storage or float32), on the host."""
     torch.cuda.synchronize()
     return t.view(torch.int32).cpu().numpy().view(np.uint32)
-
-
-def kmap(keys):
-    """Order-preserving u32 pattern of the keys: u32 as they are; f32 with the
-    sign set inverted, else the sign bit set."""
-    if keys.dtype == np.float32:
-        b = keys.view(np.uint32)
-        return np.where(b >> 31 != 0, ~b, b | np.uint32(0x80000000)).astype(np.uint32)
-    return keys
-
-
-def pairs_oracle(keys, vals):
-    order = np.lexsort((vals, kmap(keys)))
-    return keys.view(np.uint32)[order], vals[order]
-
-
-def argsort_oracle(keys):
-    return np.argsort(kmap(keys), kind="stable").astype(np.uint32)
 
 
 def tied_keys(rng, n):

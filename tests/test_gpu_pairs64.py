@@ -8,6 +8,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import misort  # noqa: E402
+from sort_oracles import order_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -52,10 +53,6 @@ def kmap(keys):
         b = keys.view(np.uint64)
         return np.where(b >> U64(63) != 0, ~b, b | U64(1 << 63)).astype(np.uint64)
     return keys
-
-
-def order_of(keys):
-    return np.argsort(kmap(keys), kind="stable")
 
 
 def rand_u32(rng, n):

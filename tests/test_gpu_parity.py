@@ -167,12 +167,14 @@ def test_merge_split_tail(ctx, case, na, nb, keep_max, kd):
 @pytest.mark.parametrize("kd", [np.uint32, np.float64])
 def test_merge_split_tail_on_another_stream(ctx, kd, keep_max):
     """compare_split(in_place_tail=True, stream=s): the copy of `local` into
-    `out` runs on torch's current stream, the merge on s; the merge must wait
-    for the copy.  The current stream is kept busy (a 2^26-key sort queued just
-    before the call), so a merge that does not wait reads `out` before the copy
-    lands.  `out` starts as zeros -- a sorted block, so the kernels'
-    preconditions hold whatever they read -- and the late copy then overwrites
-    the merge's result: the output differs from the oracle's."""
+    `out` and the merge are ordered, whatever torch's current stream is doing
+    (the copy once ran there and the merge on s, unordered; both now run on
+    s: tests/test_gpu_stream_order.py has the case with work pending on s).
+    The current stream is kept busy (a 2^26-key sort queued just
+    before the call), so a merge that does not wait for a copy behind that sort
+    reads `out` before the copy lands.  `out` starts as zeros -- a sorted block,
+    so the kernels' preconditions hold whatever they read -- and the late copy
+    then overwrites the merge's result: the output differs from the oracle's."""
     na, nb = 100000, 4096
     a = O.local_sort((1 + O.splitmix(na * 5 + 2, na, np.uint64) % (1 << 30)).astype(kd))
     b = O.local_sort((1 + O.splitmix(nb * 3 + 9, nb, np.uint64) % (1 << 30)).astype(kd))

@@ -13,6 +13,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import misort  # noqa: E402
+from sort_oracles import want_rows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -58,13 +59,6 @@ def kmap(keys):
 def kunmap(o):
     """The f64 bit pattern of an ordered u64 pattern."""
     return np.where(o >> U64(63) != 0, o & U64(0x7FFFFFFFFFFFFFFF), ~o).astype(np.uint64)
-
-
-def want_rows(keys):
-    """The oracle: bit patterns (rows, cols) of every row sorted on its own."""
-    if keys.dtype == np.float64:
-        return kunmap(np.sort(kmap(keys), axis=1))
-    return np.sort(keys, axis=1)
 
 
 def rand(rng, shape, dt):

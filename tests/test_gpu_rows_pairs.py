@@ -15,6 +15,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 import misort  # noqa: E402
+from sort_oracles import want_rows_pairs as want  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -54,14 +55,6 @@ def kunmap(o, f32):
     if not f32:
         return o
     return np.where(o >> U32(31) != 0, o & U32(0x7FFFFFFF), ~o).astype(U32)
-
-
-def want(keys, vals=None, f32=False):
-    """The oracle: (keys, values) bit patterns of every row sorted by (key, value)."""
-    rows, cols = keys.shape
-    v = np.broadcast_to(np.arange(cols, dtype=U64), (rows, cols)) if vals is None else vals.astype(U64)
-    rec = np.sort(kmap(keys, f32).astype(U64) << U64(32) | v, axis=1)
-    return kunmap((rec >> U64(32)).astype(U32), f32), (rec & U64(0xFFFFFFFF)).astype(U32)
 
 
 def rand(rng, shape):
