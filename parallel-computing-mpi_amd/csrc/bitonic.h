@@ -40,6 +40,7 @@
 
 #include "kernels.h"
 #include "lds_merge.h"
+#include "net_r4.h"
 
 // Build switch (tools/build_variant.sh): MISORT_TILE_DIRECT 0 = the SORT tiles
 // transpose their loaded keys through LDS before the register levels (see the
@@ -253,8 +254,14 @@ __device__ __forceinline__ void store_slot(K* dst, int64_t tile, int64_t n, bool
 }
 
 // Compile-time stage list on 32 register keys: relative bits TOP..TOP-CNT+1.
+// 4-byte keys: two stages at a time as 6-op radix-4 steps (net_r4.h;
+// MISORT_NET_R4 0: one stage at a time, below).
 template <typename K, int TOP, int CNT, bool FLIP>
 __device__ __forceinline__ void reg_stages_c(K (&v)[32]) {
+    if constexpr (sizeof(K) == 4 && MISORT_NET_R4 != 0) {
+        net_r4::stages_r4<TOP, CNT, FLIP>(v);
+        return;
+    }
 #pragma unroll
     for (int r = TOP; r > TOP - CNT; --r) {
         const bool fl = FLIP && r == TOP;
