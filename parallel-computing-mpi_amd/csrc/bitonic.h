@@ -1143,13 +1143,15 @@ hipError_t local_sort(const K* in, K* out, int64_t n, bool ord_in, K* scratch, h
 
 // One pass of a plan's shape (probes and tests): the SORT tile pass over n keys
 // (kind KIND_TILE_SORT; u32: hi = 13 the 2^14 tile, else 2^15), one merge level of runs of 2^hi (KIND_RUNS), or R
-// multi-way levels from runs of 2^hi (KIND_RUNSK, R = 1..4; 0: 2).
+// multi-way levels from runs of 2^hi (KIND_RUNSK, R = 1..4; 0: 2), with the
+// fence stride the local sort of n keys takes (mergek_fence_log2).
 template <typename K>
 hipError_t run_pass(const K* in, K* out, int64_t n, int kind, int hi, int R, int flip, hipStream_t s) {
     (void)flip;
     if (n <= 0) return hipSuccess;
     if (kind == KIND_RUNS) return merge_level<K>(in, out, n, hi, s);
-    if (kind == KIND_RUNSK) return mergek_build(MERGEK_FENCE_LOG2).merge_levelk(in, out, n, hi, R > 0 ? R : 2, s, 0, true, 0);
+    if (kind == KIND_RUNSK)
+        return mergek_build(mergek_fence_log2(n, (int)sizeof(K))).merge_levelk(in, out, n, hi, R > 0 ? R : 2, s, 0, true, 0);
     if (kind != KIND_TILE_SORT) return hipErrorInvalidValue;
     launch_sort<K>(in, out, n, false, s, hi + 1 == SORT_LT_MERGE ? SORT_LT_MERGE : KT<K>::LT);
     return hipGetLastError();

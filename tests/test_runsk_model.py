@@ -2,9 +2,11 @@
 
 The kernels' constants and the pass plan come from the library's own host code
 (csrc/mergek_plan.h), printed by lib/mergek_plan_dump (built by the default
-make target): nothing here is a literal copy.  The rules modelled: fences every
-FG keys of each run, packed (key, run, position/FG) so that u64 order is the
-total order; the group's fences merged; every fm-th one starts a chunk whose
+make target): nothing here is a literal copy.  The model itself (fences,
+chunk_bounds, refine, check_groups, make_keys and the dump's readers) lives in
+merge_battery.py, shared with the merge battery.  The rules modelled: fences every
+FG keys of each run in the total order (key, run, position/FG);
+the group's fences merged; every fm-th one starts a chunk whose
 start in each run is that run's count of keys before the fence; chunks are
 then merged independently.  Checks the properties the kernels rely on: chunks
 tile each group exactly, no chunk exceeds CAP keys nor the load rows (RW keys
@@ -14,205 +16,13 @@ the bounds layout -- with the worst-case fm, and with the raised fm of the
 capacity split, where a chunk over CAP is cut at its middle fence.  The plan's
 workspace layout and knob rules are checked from the dump alone
 (test_pass_layout).  K = 2^lk, lk = 1..4."""
-import functools
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DUMP = os.path.join(ROOT, "parallel-computing-mpi_amd", "lib", "mergek_plan_dump")
-ASAN_DUMP = os.path.join(ROOT, "build", "asan", "mergek_plan_dump")
-
-
-def run_dump(args, knobs=None, exe=DUMP):
-    """The dump program's JSON lines for `args`; knobs = the MISORT_* settings it
-    sees (this process's own are not passed on; the rest of the environment is)."""
-    env = {k: v for k, v in os.environ.items() if not k.startswith("MISORT_")}
-    env.update(knobs or {})
-    r = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, env=env, timeout=60)
-    assert r.returncode == 0 and r.stderr == "", (args, knobs, r.returncode, r.stderr[-2000:])
-    return [json.loads(line) for line in r.stdout.splitlines()]
-
-
-@functools.lru_cache(maxsize=None)
-def shape(lk, key_bytes=4, fgl=7):
-    """Shape<KEY, lk> and KTr<KEY> of the build with 2^fgl-key fences."""
-    return run_dump([key_bytes, lk, fgl])[0]
-
-
-def plans(ns, lw, lk, key_bytes=4, fgl=7, depth=0, knobs=None, exe=DUMP):
-    """plan_pass<KEY, lk>(n, lw, depth) for every n of ns."""
-    out = run_dump([",".join(map(str, ns)), lw, lk, key_bytes, fgl, depth], knobs, exe)
-    assert len(out) == len(ns) and all(p["ok"] for p in out)
-    return out
-
-
-FG_LOG2 = shape(1)["FG_LOG2"]  # the model runs the default build (u32 keys)
-FG = 1 << FG_LOG2
-
-
-def fences(x, lw, lk, n):
-    p = np.arange(0, n, FG, dtype=np.int64)
-    r = (p >> lw) & ((1 << lk) - 1)
-    j = (p & ((1 << lw) - 1)) >> FG_LOG2
-    return ((x[p].astype(np.uint64) << np.uint64(32)) | (r.astype(np.uint64) << np.uint64(32 - lk))
-            | j.astype(np.uint64))
-
-
-def chunk_bounds(x, lw, lk, g, F, fm):
-    """Start of every chunk of group g in each run (+ the end slot), as k_bounds;
-    and bound_at(i): the same for the group's i-th merged fence (k_split_desc)."""
-    K = 1 << lk
-    n, W = x.size, 1 << lw
-    base = g << (lw + lk)
-    lens = [max(0, min(W, n - base - r * W)) for r in range(K)]
-    f0, f1 = base >> FG_LOG2, (min(n, base + K * W) + FG - 1) >> FG_LOG2
-    M = np.sort(F[f0:f1])
-
-    def bound_at(i):
-        f = int(M[i])
-        v, r0, j0 = f >> 32, (f >> (32 - lk)) & (K - 1), f & ((1 << (32 - lk)) - 1)
-        st = []
-        for r in range(K):
-            if r == r0:
-                st.append(j0 << FG_LOG2)
-                continue
-            run = x[base + r * W: base + r * W + lens[r]]
-            want = int(np.searchsorted(run, v, side="right" if r < r0 else "left"))
-            st.append(want)
-            if lens[r] == 0:
-                continue
-            # k_bounds' two-stage search: fences of run r before f, then the
-            # FG positions between two of them
-            fr = F[(base + r * W) >> FG_LOG2: ((base + r * W) >> FG_LOG2) + ((lens[r] + FG - 1) >> FG_LOG2)]
-            lo = int(np.searchsorted(fr, np.uint64(f), side="left"))
-            got = 0 if lo == 0 else refine(run, fr, lo, lens[r], v, r < r0)
-            assert got == want
-        return st
-
-    out = [bound_at(t * fm) for t in range(0, (f1 - f0 + fm - 1) // fm)]
-    out.append(lens)
-    return out, lens, bound_at, f1 - f0
-
-
-def refine(run, fr, lo, ln, v, le):
-    """k_bounds' window search: the first position in [a, b] whose key is not
-    before the fence (key > v if le, key >= v otherwise), guessed by
-    interpolating v between the window's fence keys, bracketed by galloping
-    from the guess, then binary-searched."""
-    def before(q):
-        return run[q] <= v if le else run[q] < v
-    a, b = ((lo - 1) << FG_LOG2) + 1, min(lo << FG_LOG2, ln)
-    ka = int(fr[lo - 1]) >> 32
-    p = a + ((b - a) >> 1)
-    if (lo << FG_LOG2) < ln:
-        kb = int(fr[lo]) >> 32
-        if kb > ka:
-            p = a + ((v - ka) * (b - a)) // (kb - ka)
-    p = min(max(p, a), b)
-    if p < b and before(p):
-        lo_b, hi_b, step = p + 1, b, 4
-        while lo_b + step - 1 < hi_b:
-            x = lo_b + step - 1
-            if before(x):
-                lo_b, step = x + 1, step * 2
-            else:
-                hi_b = x
-                break
-    else:
-        lo_b, hi_b, step = a, p, 4
-        while hi_b - step >= lo_b:
-            x = hi_b - step
-            if not before(x):
-                hi_b, step = x, step * 2
-            else:
-                lo_b = x + 1
-                break
-    while lo_b < hi_b:
-        mid = (lo_b + hi_b) >> 1
-        if before(mid):
-            lo_b = mid + 1
-        else:
-            hi_b = mid
-    return lo_b
-
-
-def make_keys(kind, n, lw, lk, seed, fm=0):
-    K, W = 1 << lk, 1 << lw
-    rng = np.random.default_rng(seed)
-    if kind == "uniform":
-        x = rng.integers(0, 2**32, n, dtype=np.uint64).astype(np.uint32)
-    elif kind == "dup":
-        x = rng.integers(0, 7, n).astype(np.uint32)
-    elif kind == "equal":
-        x = np.full(n, 0xFFFFFFFF, np.uint32)
-    elif kind == "interleaved":
-        x = (np.arange(n) % K * 1000 + np.arange(n) // K).astype(np.uint32)
-    else:
-        # "clumped" (for chunks cut every fm fences): after a prefix of zeros, every
-        # run repeats a period of c + 1 fences, c = ceil(fm / K) -- one key 2m + 1,
-        # then (c + 1) FG - 1 keys 2m + 2 holding c fences.  The prefixes hold
-        # fm - K fences in all, so the group's chunk 1 starts at run 0's first
-        # fence of the first clump and takes nearly that whole clump from every
-        # run: its window offsets add up instead of cancelling, and it exceeds CAP.
-        c, i = -(-fm // K), np.arange(n)
-        r, pos = (i >> lw) & (K - 1), i & (W - 1)
-        q = pos - ((fm - K) // K + (r < (fm - K) % K)) * FG
-        per = (c + 1) * FG
-        x = np.where(q < 0, 0, 1 + 2 * (q // per) + (q % per != 0)).astype(np.uint32)
-    for s in range(0, n, W):
-        x[s:s + W].sort()
-    return x
-
-
-def check_groups(x, lw, lk, fm, groups, split):
-    """The chunking invariants on the given groups of x, cut every fm merged
-    fences; split: a chunk over CAP is cut at its middle merged fence into two
-    (k_chunk_desc lists it, k_split_desc cuts it) and each half must fit.
-    Returns the number of chunks cut."""
-    S = shape(lk)
-    K, CAP, RW, NROWS = S["K"], S["CAP"], S["RW"], S["NROWS"]
-    n, W = x.size, 1 << lw
-    F = fences(x, lw, lk, n)
-    kf = ((K * W >> FG_LOG2) + fm - 1) // fm
-    ncut = 0
-    for g in groups:
-        bounds, lens, bound_at, nfg = chunk_bounds(x, lw, lk, g, F, fm)
-        if (g + 1) * K * W <= n:
-            assert len(bounds) - 1 == kf
-        base = g << (lw + lk)
-        merged = []
-        prev_max = None
-        assert bounds[0] == [0] * K
-        pieces = []
-        for t, (a, b) in enumerate(zip(bounds[:-1], bounds[1:])):
-            size = sum(b[r] - a[r] for r in range(K))
-            if split and size > CAP:
-                mid = min(fm, nfg - t * fm) // 2
-                assert mid > 0
-                m = bound_at(t * fm + mid)
-                pieces += [(a, m), (m, b)]
-                ncut += 1
-            else:
-                pieces.append((a, b))
-        for a, b in pieces:
-            seg = [x[base + r * W + a[r]: base + r * W + b[r]] for r in range(K)]
-            size = sum(s.size for s in seg)
-            assert all(0 <= a[r] <= b[r] <= lens[r] for r in range(K)) and size <= CAP
-            # load rows: each row of RW keys inside one segment, NROWS per chunk
-            assert sum(-(-s.size // RW) for s in seg) <= NROWS
-            chunk = np.sort(np.concatenate(seg))
-            if chunk.size and prev_max is not None:
-                assert chunk[0] >= prev_max
-            if chunk.size:
-                prev_max = chunk[-1]
-            merged.append(chunk)
-        want = np.sort(x[base: base + sum(lens)])
-        np.testing.assert_array_equal(np.concatenate(merged), want)
-    return ncut
+from merge_battery import (ASAN_DUMP, FG, FG_LOG2, check_groups, chunk_bounds, fences, make_keys, plans,  # noqa: F401
+                           refine, run_dump, shape)
 
 
 @pytest.mark.parametrize("lk", [1, 2, 3, 4])
