@@ -333,6 +333,21 @@ int rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int* block
 // (one lane's registers).
 constexpr int ROWS_LR_MIN = 5;
 
+// Row-wise top-k of 32-bit keys (topk.hip): one pass of the plan of topk_plan.h
+// over every row.  It sorts blocks of 2^p.lr ascending records T(key) << 32 |
+// column in the u64 row tile (T = K or, largest, ~K; K the identity or, f32,
+// ord_of_f32) and keeps the first k of each.  Exactly one source: keys_in (the
+// caller's rows x p.m_in keys; the records are formed in registers) or recs_in
+// (rows x p.m_in candidate records).  p.npieces > 1: the candidates go to
+// recs_out[(row p.npieces + piece) k + j]; p.npieces == 1, the last pass:
+// keys_out (may be null) / idx_out[row k + j].  No output may overlap an input.
+// Element alignment; 16-byte key loads when keys_in is 16-byte aligned and
+// p.m_in a multiple of 4.  One KIND_TILE_SORT record of the bytes read and written.
+struct TopkPass;
+hipError_t topk_pass(const TopkPass& p, const uint32_t* keys_in, const uint64_t* recs_in, uint64_t* recs_out,
+                     uint32_t* keys_out, uint32_t* idx_out, int64_t rows, int64_t k, bool f32, bool largest,
+                     hipStream_t s, LaunchHook* hook);
+
 // Segmented sort (segs.hip, segs_tile.h): segment i of a caller's array is
 // [off[i], off[i + 1]), off a device array of nseg + 1 int64; its class is
 // segment_class(len) of segs_class.h, which also lays out the header.

@@ -6,6 +6,7 @@
 // (psort.cc:121,146), check_sort (psort.cc:497-520), pinned host staging and
 // per-launch HIP-event profiling.  No exception crosses the C-ABI.
 #include "misort.h"
+#include "misort_topk.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -29,6 +30,7 @@
 
 #include "kernels.h"
 #include "segs_class.h"
+#include "topk_plan.h"
 
 namespace {
 
@@ -2183,6 +2185,76 @@ int misort_rows_plan(int64_t cols, int key_bytes, int* path, int* tile_log2, int
     if (cols < 0 || !path || !tile_log2 || !block_log2) return fail(MISORT_E_INVALID, "bad rows_plan arguments");
     if (max_passes > 0 && !passes) return fail(MISORT_E_INVALID, "null passes");
     return misort::rows_plan(cols, key_bytes, path, tile_log2, block_log2, passes, max_passes < 0 ? 0 : max_passes);
+}
+
+// Row-wise top-k (topk.hip): the passes of topk_plan.h, every one a launch of the
+// tile kernel on s.  The first reads the caller's keys, the last writes the
+// caller's outputs; the candidates between them alternate between rowpad and
+// pong, both grown before the first launch (growing one frees it, which waits
+// for the device).
+int misort_local_topk_rows(misort_ctx* c, int key_dtype, const void* keys_in, void* keys_out, void* idx_out,
+                           int64_t rows, int64_t cols, int64_t k, int largest, void* stream) {
+    if (!c) return fail(MISORT_E_INVALID, "null ctx");
+    if (!valid_pair_dtype(key_dtype))
+        return fail(MISORT_E_INVALID, "local_topk_rows takes MISORT_U32 or MISORT_F32 keys, got %d", key_dtype);
+    if (rows < 0 || cols < 0 || k < 0) return fail(MISORT_E_INVALID, "bad local_topk_rows arguments");
+    if (rows == 0 || k == 0) return MISORT_OK;
+    if (cols > misort::TOPK_COLS_MAX)
+        return fail(MISORT_E_INVALID, "local_topk_rows: rows of %lld keys: a column index must stay below 2^31",
+                    (long long)cols);
+    if (k > cols)
+        return fail(MISORT_E_INVALID, "local_topk_rows: k = %lld of rows of %lld keys", (long long)k, (long long)cols);
+    if (!misort::topk_shape_ok(cols, k))
+        return fail(MISORT_E_INVALID,
+                    "local_topk_rows: k = %lld of rows of %lld keys: rows longer than 2^%d take k <= %lld "
+                    "(sort the rows with misort_local_sort_rows_pairs and take the first k columns)",
+                    (long long)k, (long long)cols, misort::TOPK_LT, (long long)misort::TOPK_K_LONG_MAX);
+    if (rows > (INT64_MAX >> 4) / cols)
+        return fail(MISORT_E_INVALID, "local_topk_rows: %lld x %lld keys are too many", (long long)rows,
+                    (long long)cols);
+    if (!keys_in || !idx_out) return fail(MISORT_E_INVALID, "bad local_topk_rows arguments");
+    const uint64_t in_bytes = (uint64_t)rows * (uint64_t)cols * 4, out_bytes = (uint64_t)rows * (uint64_t)k * 4;
+    // a tile stores its rows' results while other tiles still read theirs
+    if (ranges_overlap(keys_out, out_bytes, keys_in, in_bytes) || ranges_overlap(idx_out, out_bytes, keys_in, in_bytes))
+        return fail(MISORT_E_INVALID, "local_topk_rows: an output overlaps d_keys_in");
+    if (ranges_overlap(keys_out, out_bytes, idx_out, out_bytes))
+        return fail(MISORT_E_INVALID, "local_topk_rows: d_keys_out overlaps d_idx_out");
+    misort::TopkPass plan[misort::TOPK_MAX_PASSES];
+    const int np = misort::topk_plan(cols, k, plan, misort::TOPK_MAX_PASSES);
+    if (np < 1 || np > misort::TOPK_MAX_PASSES) return fail(MISORT_E_INTERNAL, "local_topk_rows: no plan");
+    int rc;
+    // pass i writes buffer i % 2: rowpad holds the first pass's candidates, pong the second's
+    if (np > 1 && (rc = c->rowpad.ensure((size_t)rows * (size_t)plan[0].m_out * 8))) return rc;
+    if (np > 2 && (rc = c->pong.ensure((size_t)rows * (size_t)plan[1].m_out * 8))) return rc;
+    hipStream_t s = pick(c, stream);
+    const bool f32 = key_dtype == MISORT_F32;
+    for (int i = 0; i < np; ++i) {
+        const bool first = i == 0, last = i == np - 1;
+        const uint64_t* src = first ? nullptr : (const uint64_t*)(i % 2 ? c->rowpad.p : c->pong.p);
+        uint64_t* dst = last ? nullptr : (uint64_t*)(i % 2 ? c->pong.p : c->rowpad.p);
+        const hipError_t e = misort::topk_pass(plan[i], first ? (const uint32_t*)keys_in : nullptr, src, dst,
+                                               last ? (uint32_t*)keys_out : nullptr, last ? (uint32_t*)idx_out : nullptr,
+                                               rows, k, f32, largest != 0, s, hook(c));
+        if (e != hipSuccess) return fail(MISORT_E_HIP, "topk_pass %d of %d: %s", i + 1, np, hipGetErrorString(e));
+    }
+    return MISORT_OK;
+}
+
+int misort_topk_plan(int64_t cols, int64_t k, int* passes, int max_passes) {
+    if (max_passes > 0 && !passes) return fail(MISORT_E_INVALID, "null passes");
+    misort::TopkPass plan[misort::TOPK_MAX_PASSES];
+    const int np = misort::topk_plan(cols, k, plan, misort::TOPK_MAX_PASSES);
+    if (np < 0)
+        return fail(MISORT_E_INVALID,
+                    "topk_plan: 1 <= k <= cols <= 2^31 is needed, and k <= %lld for cols > 2^%d; got cols = %lld, k = %lld",
+                    (long long)misort::TOPK_K_LONG_MAX, misort::TOPK_LT, (long long)cols, (long long)k);
+    for (int i = 0; i < np && i < max_passes; ++i) {
+        passes[4 * i] = (int)(uint32_t)plan[i].m_in;  // 2^31: its unsigned 32-bit pattern
+        passes[4 * i + 1] = plan[i].lr;
+        passes[4 * i + 2] = (int)plan[i].npieces;
+        passes[4 * i + 3] = (int)plan[i].m_out;
+    }
+    return np;
 }
 
 // Segmented sort: segment i is [off[i], off[i + 1]).  A count kernel validates

@@ -20,7 +20,7 @@ __all__ = [
     "U32", "U64", "F64", "F32", "MisortError", "NotPowerOfTwo", "NativeLibraryMissing",
     "library_path", "lib", "Context", "Group", "block_sizes", "schedule", "tile_log2", "plan",
     "sample_indices", "exchange_count", "set_shared_gpu_env", "rows_plan",
-    "segment_class",
+    "segment_class", "topk_plan",
 ]
 
 U32, U64, F64 = 0, 1, 2
@@ -85,6 +85,8 @@ def lib():
         "misort_local_sort_rows_pairs": ([vp, i32, vp, vp, vp, vp, i64, i64, vp], i32),
         "misort_rows_plan": ([i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32),
                               ctypes.POINTER(i32), i32], i32),
+        "misort_local_topk_rows": ([vp, i32, vp, vp, vp, i64, i64, i64, i32, vp], i32),
+        "misort_topk_plan": ([i64, i64, ctypes.POINTER(i32), i32], i32),
         "misort_local_sort_segments": ([vp, i32, vp, vp, i64, vp, i64, vp], i32),
         "misort_segment_class": ([i64, i32], i32),
         "misort_merge_split": ([vp, i32, vp, i64, vp, i64, vp, i32, vp], i32),
@@ -202,6 +204,20 @@ def rows_plan(cols, key_bytes=4):
     return {"path": ("tile", "blocks")[path.value], "tile_log2": tile.value, "block_log2": block.value,
             "passes": [(KIND_NAMES[buf[4 * i]], buf[4 * i + 1], buf[4 * i + 2], bool(buf[4 * i + 3]))
                        for i in range(np_)]}
+
+
+def topk_plan(cols, k):
+    """The passes of Context.topk_rows for rows of ``cols`` keys:
+    ``[(m_in, LR, npieces, m_out)]``.  A pass cuts every row of m_in records into
+    npieces blocks of 2^LR virtual records, sorts each in an LDS tile and keeps
+    the first k: m_out = npieces * k records per row.  The first pass reads the
+    keys, the last (npieces == 1) writes the outputs.  A (cols, k) that top-k
+    does not take is a MisortError (code -1)."""
+    np_ = _check(lib().misort_topk_plan(cols, k, None, 0))
+    buf = (ctypes.c_int32 * (4 * max(np_, 1)))()
+    _check(lib().misort_topk_plan(cols, k, buf, np_))
+    # m_in reaches 2^31: stored as its unsigned 32-bit pattern
+    return [(buf[4 * i] & 0xFFFFFFFF, buf[4 * i + 1], buf[4 * i + 2], buf[4 * i + 3]) for i in range(np_)]
 
 
 def segment_class(len, key_bytes=4):
@@ -626,6 +642,61 @@ class Context:
         _check(lib().misort_local_sort_rows_pairs(self._h, dt, _ptr(keys), None, None, _ptr(out), rows, cols,
                                                   self._stream(stream)))
         return out
+
+    def _topk_out(self, name, out, like, dtype, shape, n):
+        """An output of topk_rows: a new tensor of ``shape``, or the first n
+        elements of the caller's tensor seen in that shape."""
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=like.device)
+        _span_check(n, **{name: out})
+        if out.device != like.device:
+            raise ValueError(f"{name} is on {out.device}, the keys are on {like.device}")
+        return out if tuple(out.shape) == tuple(shape) else out.view(-1)[:n].view(shape)
+
+    def topk_rows(self, keys, k, largest=True, out_values=None, out_indices=None, stream=None):
+        """The k largest (``largest=True``) or smallest keys along the last
+        dimension of a contiguous tensor of rank >= 1, and their columns:
+        ``(values, indices)`` of shape ``keys.shape[:-1] + (k,)``, what
+        ``torch.topk(keys, k, dim=-1, largest=largest, sorted=True)`` returns,
+        without sorting the rows.  Keys are u32 (uint32/int32 storage, compared
+        unsigned) or float32 in the total order of sort_rows_pairs (largest:
+        positive NaNs first, then +inf ... +0.0, -0.0 ... -inf, negative NaNs
+        last; smallest: the reverse), every value bit-exact.  Each row is sorted,
+        best first; equal keys come out in ascending column order in both
+        directions.  ``values`` has the keys' dtype, ``indices`` the storage of
+        argsort_rows (like u32 keys, int32 for float keys): 32-bit columns where
+        torch returns int64.  ``1 <= k <= shape[-1] <= 2^31``, and ``k <= 1024``
+        for rows longer than 2^13 (else MisortError, code -1: use argsort_rows);
+        ``k == 0`` gives empty outputs.  The outputs must not overlap the keys
+        or each other (MisortError, code -1); the keys are left unchanged.  A
+        non-contiguous tensor, rank 0, a negative k and a too-small output raise
+        ValueError, wrong dtypes TypeError.  ``topk_plan(cols, k)`` tells the
+        passes."""
+        return self._topk_rows("topk_rows", keys, k, largest, True, out_values, out_indices, stream)
+
+    def topk_rows_indices(self, keys, k, largest=True, out=None, stream=None):
+        """The ``indices`` of topk_rows alone: no keys are written."""
+        return self._topk_rows("topk_rows_indices", keys, k, largest, False, None, out, stream)[1]
+
+    def _topk_rows(self, what, keys, k, largest, with_values, out_values, out_indices, stream):
+        import torch
+        dt = _pair_key_dtype(keys)
+        rows, cols = self._rows_pairs_shape(what, keys)
+        k = int(k)
+        if k < 0:
+            raise ValueError(f"{what}: negative k {k}")
+        if out_values is not None and out_values.dtype != keys.dtype:
+            raise TypeError(f"out_values is {out_values.dtype}, the keys are {keys.dtype}")
+        _pair_values(out_indices, "out_indices")
+        shape, n = tuple(keys.shape[:-1]) + (k,), rows * k
+        values = self._topk_out("out_values", out_values, keys, keys.dtype, shape, n) if with_values else None
+        indices = self._topk_out("out_indices", out_indices, keys,
+                                 keys.dtype if _u32_storage(keys) else torch.int32, shape, n)
+        _check(lib().misort_local_topk_rows(self._h, dt, _ptr(keys), _ptr(values) if with_values else None,
+                                            _ptr(indices), rows, cols, k, 1 if largest else 0,
+                                            self._stream(stream)))
+        return values, indices
 
     def sort_pairs64(self, keys, values, out_keys=None, out_values=None, n=None, stream=None):
         """Stable key-value sort of 64-bit keys on this GPU: the pairs ascending
