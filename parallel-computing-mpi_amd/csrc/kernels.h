@@ -377,6 +377,31 @@ hipError_t pad_segs(const void* in, const int64_t* off, const uint32_t* list, in
 hipError_t unpad_segs(const void* pad, void* out, const int64_t* off, const uint32_t* list, int64_t count,
                       int64_t keys, int k, int key_bytes, bool f64, hipStream_t s, LaunchHook* hook);
 
+// Segmented key-value sort of 32-bit keys with 32-bit values (segs_pairs.hip):
+// every segment ascending by the record K(key) << 32 | value, K the identity or
+// (f32) ord_of_f32.  The offset sweeps, the classes and the lists are the ones
+// above with key_bytes = 8.  vals_in null: the value of element begin + c is c;
+// keys_out null: no keys are written.  An output may be exactly an input.
+//   sort_segs_pairs_tile  one class lr = 5..13: the `count` segments of `list`,
+//                   2^(13 - lr) per u64 LDS tile, the record formed in registers
+//                   as the tile loads and split as it stores.  One KIND_TILE_SORT
+//                   record of the bytes of the arrays in use (4 `keys` each);
+//   pad_segs_pairs  one class k > 13: pad[r << k | c] = the record of element
+//                   begin + c for c < len of segment list[r], all-ones above;
+//   unpad_segs_pairs  keys_out / vals_out[begin + c] from pad[r << k | c], c < len.
+// pad is 16-byte aligned; the caller's arrays need 4-byte alignment only.
+// Records of KIND_OTHER: pad counts the caller's arrays it reads and count 2^k
+// records, unpad `keys` records and the arrays it writes.
+hipError_t sort_segs_pairs_tile(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out,
+                                uint32_t* vals_out, const int64_t* off, const uint32_t* list, int64_t count, int lr,
+                                int64_t keys, bool f32, hipStream_t s, LaunchHook* hook);
+hipError_t pad_segs_pairs(const uint32_t* keys_in, const uint32_t* vals_in, const int64_t* off, const uint32_t* list,
+                          int64_t count, int64_t keys, uint64_t* pad, int k, bool f32, hipStream_t s,
+                          LaunchHook* hook);
+hipError_t unpad_segs_pairs(const uint64_t* pad, uint32_t* keys_out, uint32_t* vals_out, const int64_t* off,
+                            const uint32_t* list, int64_t count, int64_t keys, int k, bool f32, hipStream_t s,
+                            LaunchHook* hook);
+
 // Counter-based SplitMix64 keys for global indices [g0, g0+n) (bench/test input).
 hipError_t fill_splitmix_u32(uint32_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);
 hipError_t fill_splitmix_u64(uint64_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);

@@ -7,6 +7,7 @@
 // per-launch HIP-event profiling.  No exception crosses the C-ABI.
 #include "misort.h"
 #include "misort_topk.h"
+#include "misort_segments_pairs.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -2354,6 +2355,125 @@ int misort_local_sort_segments(misort_ctx* c, int dtype, const void* in, void* o
         if ((rc = sort_row_blocks(c, count, k, kb, s, "segment blocks"))) return rc;
         e = misort::unpad_segs(c->rowpad.p, out, offsets, lists + base[k], count, keys, k, (int)kb, f64, s, hook(c));
         if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::unpad_segs (class %d): %s", k, hipGetErrorString(e));
+    }
+    return MISORT_OK;
+}
+
+// Segmented key-value sort, 32-bit keys: misort_local_sort_segments step for
+// step on u64 records that exist in registers only (classes up to the u64 SORT
+// tile) or in the padded blocks (longer classes): segs_pairs.hip.  The classes
+// are those of 8-byte keys; the offset sweeps, the header and the lists are the
+// keys-only call's.
+int misort_local_sort_segments_pairs(misort_ctx* c, int key_dtype, const void* keys_in, const void* vals_in,
+                                     void* keys_out, void* vals_out, int64_t n, const int64_t* offsets,
+                                     int64_t nseg, void* stream) {
+    if (!c) return fail(MISORT_E_INVALID, "null ctx");
+    if (!valid_pair_dtype(key_dtype))
+        return fail(MISORT_E_INVALID, "local_sort_segments_pairs takes MISORT_U32 or MISORT_F32 keys, got %d",
+                    key_dtype);
+    if (n < 0 || nseg < 0 || nseg > 0x7FFFFFFFll)
+        return fail(MISORT_E_INVALID, "bad local_sort_segments_pairs arguments (0 <= n, 0 <= nseg <= 2^31 - 1)");
+    // the padded blocks of the long classes (under 2 n records of 8 bytes) must be addressable too
+    if (n > (INT64_MAX >> 5))
+        return fail(MISORT_E_INVALID, "local_sort_segments_pairs: %lld pairs are too many", (long long)n);
+    const uint64_t bytes = (uint64_t)n * 4, off_bytes = ((uint64_t)nseg + 1) * 8;
+    // a tile or a pad sweep reads segments another workgroup may already have rewritten,
+    // and every kernel reads the offsets while the outputs are written
+    if ((keys_out != keys_in && ranges_overlap(keys_out, bytes, keys_in, bytes)) ||
+        (vals_out != vals_in && ranges_overlap(vals_out, bytes, vals_in, bytes)))
+        return fail(MISORT_E_INVALID,
+                    "local_sort_segments_pairs: an output overlaps its input (only d_keys_out == d_keys_in and "
+                    "d_vals_out == d_vals_in are allowed)");
+    if (ranges_overlap(keys_out, bytes, vals_out, bytes) || ranges_overlap(keys_out, bytes, vals_in, bytes) ||
+        ranges_overlap(vals_out, bytes, keys_in, bytes) || ranges_overlap(keys_in, bytes, vals_in, bytes))
+        return fail(MISORT_E_INVALID, "local_sort_segments_pairs: the key and value arrays overlap");
+    if (nseg > 0 && (ranges_overlap(keys_out, bytes, offsets, off_bytes) ||
+                     ranges_overlap(vals_out, bytes, offsets, off_bytes)))
+        return fail(MISORT_E_INVALID, "local_sort_segments_pairs: an output overlaps d_offsets");
+    if (n == 0) return MISORT_OK;  // no array is looked at: empty ones may be null
+    if (!keys_in || !vals_out) return fail(MISORT_E_INVALID, "bad local_sort_segments_pairs arguments");
+    if (((uintptr_t)keys_in | (uintptr_t)vals_in | (uintptr_t)keys_out | (uintptr_t)vals_out) & 3)
+        return fail(MISORT_E_INVALID, "local_sort_segments_pairs: an array is not 4-byte aligned");
+    hipStream_t s = pick(c, stream);
+    // [k0, k1) of the outputs that have an input, out of place
+    const auto copy = [&](int64_t k0, int64_t k1) -> int {
+        if (k1 <= k0) return MISORT_OK;
+        const size_t at = (size_t)k0 * 4, len = (size_t)(k1 - k0) * 4;
+        if (keys_out && keys_out != keys_in)
+            HIPCHK(hipMemcpyAsync((char*)keys_out + at, (const char*)keys_in + at, len, hipMemcpyDeviceToDevice, s));
+        if (vals_in && vals_out != vals_in)
+            HIPCHK(hipMemcpyAsync((char*)vals_out + at, (const char*)vals_in + at, len, hipMemcpyDeviceToDevice, s));
+        return MISORT_OK;
+    };
+    if (nseg == 0) return copy(0, n);
+    if (!offsets) return fail(MISORT_E_INVALID, "bad local_sort_segments_pairs arguments");
+    if ((uintptr_t)offsets & 7)
+        return fail(MISORT_E_INVALID, "local_sort_segments_pairs: d_offsets is not 8-byte aligned");
+
+    int rc = c->segs.ensure(misort::SEG_LIST_BYTES + (size_t)nseg * sizeof(uint32_t));
+    if (rc) return rc;
+    char* hdr = (char*)c->segs.p;
+    uint32_t* lists = (uint32_t*)(hdr + misort::SEG_LIST_BYTES);
+    HIPCHK(hipMemsetAsync(hdr, 0, misort::SEG_H_WORDS * 8, s));
+    hipError_t e = misort::seg_count(offsets, nseg, n, 8, hdr, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::seg_count: %s", hipGetErrorString(e));
+    int64_t h[misort::SEG_H_WORDS];
+    if ((rc = fetch(c, s, {{h, hdr, misort::SEG_H_FETCH * 8}}))) return rc;  // the call's one host wait
+    if (h[misort::SEG_H_BAD] != 0)
+        return fail(MISORT_E_INVALID,
+                    "local_sort_segments_pairs: malformed offsets: %lld of %lld segments, the first at index %lld "
+                    "(0 <= offsets[i] <= offsets[i + 1] <= n = %lld is needed); nothing was written",
+                    (long long)h[misort::SEG_H_BAD], (long long)nseg, (long long)~h[misort::SEG_H_BAD_AT], (long long)n);
+    // the class lists, class after class; the long classes' blocks
+    const int lt = misort::seg_tile_log2(8);
+    int64_t base[misort::SEG_CLASSES], listed = 0, blocks_max = 0;
+    for (int k = 0; k < misort::SEG_CLASSES; ++k) {
+        base[k] = listed;
+        listed += h[misort::SEG_H_COUNT + k];
+        if (k > lt && h[misort::SEG_H_COUNT + k] > 0) blocks_max = std::max(blocks_max, h[misort::SEG_H_COUNT + k] << k);
+        // class k > 32 holds the lengths above 2^32 only
+        if (!vals_in && k > 32 && h[misort::SEG_H_COUNT + k] > 0)
+            return fail(MISORT_E_INVALID,
+                        "argsort of segments: %lld segments are longer than 2^32 keys (a 32-bit value holds 2^32 "
+                        "positions); nothing was written",
+                        (long long)h[misort::SEG_H_COUNT + k]);
+    }
+    if (listed > nseg)
+        return fail(MISORT_E_INTERNAL, "local_sort_segments_pairs: the count kernel listed too many segments");
+    if ((rc = copy(0, h[misort::SEG_H_FIRST])) || (rc = copy(h[misort::SEG_H_LAST], n))) return rc;
+    if (listed == 0) return MISORT_OK;  // every segment is empty
+    // (both scratch buffers before the first key kernel: growing one frees it, which waits for the device)
+    if (blocks_max > 0) {
+        if ((rc = c->rowpad.ensure((size_t)blocks_max * 8)) || (rc = c->pong.ensure((size_t)blocks_max * 8)))
+            return rc;
+    }
+    if ((rc = h2d(c, hdr + misort::SEG_H_CURSOR * 8, base, sizeof(base), s))) return rc;
+    e = misort::seg_scatter(offsets, nseg, 8, hdr + misort::SEG_H_CURSOR * 8, lists, listed, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::seg_scatter: %s", hipGetErrorString(e));
+    const bool f32 = key_dtype == MISORT_F32;
+    const uint32_t* ki = (const uint32_t*)keys_in;
+    const uint32_t* vi = (const uint32_t*)vals_in;
+    uint32_t* ko = (uint32_t*)keys_out;
+    uint32_t* vo = (uint32_t*)vals_out;
+    for (int lr = misort::SEG_LR_MIN; lr <= lt; ++lr) {
+        const int64_t count = h[misort::SEG_H_COUNT + lr], keys = h[misort::SEG_H_KEYS + lr];
+        if (count == 0) continue;
+        e = misort::sort_segs_pairs_tile(ki, vi, ko, vo, offsets, lists + base[lr], count, lr, keys, f32, s, hook(c));
+        if (e != hipSuccess)
+            return fail(MISORT_E_HIP, "misort::sort_segs_pairs_tile (class %d): %s", lr, hipGetErrorString(e));
+    }
+    // a class's pad has read all its pairs before its sort starts, its unpad writes only its own segments
+    for (int k = lt + 1; k < misort::SEG_CLASSES; ++k) {
+        const int64_t count = h[misort::SEG_H_COUNT + k], keys = h[misort::SEG_H_KEYS + k];
+        if (count == 0) continue;
+        e = misort::pad_segs_pairs(ki, vi, offsets, lists + base[k], count, keys, (uint64_t*)c->rowpad.p, k, f32, s,
+                                   hook(c));
+        if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::pad_segs_pairs (class %d): %s", k, hipGetErrorString(e));
+        if ((rc = sort_row_blocks(c, count, k, 8, s, "segment blocks of records"))) return rc;
+        e = misort::unpad_segs_pairs((const uint64_t*)c->rowpad.p, ko, vo, offsets, lists + base[k], count, keys, k,
+                                     f32, s, hook(c));
+        if (e != hipSuccess)
+            return fail(MISORT_E_HIP, "misort::unpad_segs_pairs (class %d): %s", k, hipGetErrorString(e));
     }
     return MISORT_OK;
 }

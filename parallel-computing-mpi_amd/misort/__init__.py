@@ -88,6 +88,7 @@ def lib():
         "misort_local_topk_rows": ([vp, i32, vp, vp, vp, i64, i64, i64, i32, vp], i32),
         "misort_topk_plan": ([i64, i64, ctypes.POINTER(i32), i32], i32),
         "misort_local_sort_segments": ([vp, i32, vp, vp, i64, vp, i64, vp], i32),
+        "misort_local_sort_segments_pairs": ([vp, i32, vp, vp, vp, vp, i64, vp, i64, vp], i32),
         "misort_segment_class": ([i64, i32], i32),
         "misort_merge_split": ([vp, i32, vp, i64, vp, i64, vp, i32, vp], i32),
         "misort_merge_split_tail": ([vp, i32, vp, i64, vp, i64, i32, vp], i32),
@@ -641,6 +642,87 @@ class Context:
         out = self._pair_outputs(keys, None, None, out, keys.numel())
         _check(lib().misort_local_sort_rows_pairs(self._h, dt, _ptr(keys), None, None, _ptr(out), rows, cols,
                                                   self._stream(stream)))
+        return out
+
+    def _segments_pairs_check(self, what, keys, offsets, **others):
+        """The shape and device checks of the segmented key-value sorts (those
+        of sort_segments); returns the number of segments."""
+        import torch
+        if offsets.dtype != torch.int64:
+            raise TypeError(f"offsets is {offsets.dtype}, int64 is needed")
+        if keys.dim() != 1:
+            raise ValueError(f"{what} needs a 1-D key tensor, got {tuple(keys.shape)}")
+        if offsets.dim() != 1 or offsets.numel() < 1 or not offsets.is_contiguous():
+            raise ValueError("offsets: a contiguous 1-D tensor of at least one element is needed, "
+                             f"got {tuple(offsets.shape)} with strides {tuple(offsets.stride())}")
+        if offsets.device != keys.device:
+            raise ValueError(f"offsets is on {offsets.device}, the keys are on {keys.device}")
+        for name, t in others.items():
+            if t is not None and t.device != keys.device:
+                raise ValueError(f"{name} is on {t.device}, the keys are on {keys.device}")
+        return offsets.numel() - 1
+
+    def sort_segments_pairs(self, keys, offsets, values=None, out_keys=None, out_values=None, stream=None):
+        """Key-value sort of variable-length segments of the 1-D contiguous
+        tensors ``keys`` and ``values``: segment i is the pairs
+        ``[offsets[i], offsets[i + 1])``, sorted on its own, ascending by
+        (key, value), values compared unsigned: the order of sort_rows_pairs,
+        segment by segment.  Keys are u32 (uint32/int32 storage) or float32
+        (total order of the bit patterns: -0.0 before +0.0, negative NaNs first,
+        positive NaNs last, every key bit-exact); values are uint32/int32
+        storage of the keys' shape.  ``offsets`` is as in sort_segments: a 1-D
+        contiguous int64 tensor on the keys' device with at least one element,
+        non-decreasing, within [0, keys.numel()]; empty segments are allowed.
+        ``values=None``: the value of a pair is its position inside its segment,
+        so ``out_values`` is the stable argsort of every segment (32-bit
+        indices; ``keys[offsets[i] + idx]`` gathers the sorted segment); no
+        segment may then be longer than 2^32 keys.
+
+        The default outputs are NEW tensors and the inputs are left unchanged;
+        pairs outside the segments are copied to the outputs that have an input
+        (with ``values=None`` those elements of ``out_values`` are not written).
+        ``out_keys=keys`` and ``out_values=values`` sort in place and leave the
+        pairs outside the segments alone.  Any other overlap among the four
+        tensors, or of an output with ``offsets``, is a MisortError (code -1).
+
+        The call waits once on its stream: the host waits for a kernel that
+        validates and counts the segments (so the call cannot be captured in a
+        graph); malformed offsets are a MisortError (code -1) naming the first
+        bad index, and nothing is written then.  Wrong dtypes raise TypeError;
+        wrong shapes, non-contiguous tensors, a too-small output and a tensor on
+        another device ValueError.  Returns ``(out_keys, out_values)``."""
+        import torch
+        dt = _pair_key_dtype(keys)
+        _pair_values(values)
+        nseg = self._segments_pairs_check("sort_segments_pairs", keys, offsets, values=values, out_keys=out_keys,
+                                          out_values=out_values)
+        if values is not None and values.shape != keys.shape:
+            raise ValueError(f"values have shape {tuple(values.shape)}, the keys {tuple(keys.shape)}")
+        out_keys = torch.empty_like(keys) if out_keys is None else out_keys
+        out_values = self._pair_outputs(keys, values, out_keys, out_values, keys.numel())
+        _check(lib().misort_local_sort_segments_pairs(self._h, dt, _ptr(keys),
+                                                      _ptr(values) if values is not None else None, _ptr(out_keys),
+                                                      _ptr(out_values), keys.numel(), _ptr(offsets), nseg,
+                                                      self._stream(stream)))
+        return out_keys, out_values
+
+    def argsort_segments(self, keys, offsets, out=None, stream=None):
+        """The stable argsort of every segment of the 1-D contiguous tensor of
+        u32 or float32 keys (order and ``offsets`` as in sort_segments_pairs):
+        ``out[offsets[i] + j]`` is the position, inside segment i, of the
+        segment's j-th smallest key, equal keys in input order, so
+        ``keys[offsets[i] + out[offsets[i] + j]]`` is that key.  No keys are
+        written, and elements of ``out`` outside the segments are not written.
+        ``out`` is uint32/int32 storage (default: a new tensor of the keys'
+        shape, like u32 keys, int32 for float keys); it must not overlap
+        ``keys`` or ``offsets`` (MisortError, code -1).  No segment may be
+        longer than 2^32 keys.  The call waits once on its stream, as
+        sort_segments_pairs does, and refuses malformed offsets the same way."""
+        dt = _pair_key_dtype(keys)
+        nseg = self._segments_pairs_check("argsort_segments", keys, offsets, out=out)
+        out = self._pair_outputs(keys, None, None, out, keys.numel())
+        _check(lib().misort_local_sort_segments_pairs(self._h, dt, _ptr(keys), None, None, _ptr(out), keys.numel(),
+                                                      _ptr(offsets), nseg, self._stream(stream)))
         return out
 
     def _topk_out(self, name, out, like, dtype, shape, n):
