@@ -402,6 +402,36 @@ hipError_t unpad_segs_pairs(const uint64_t* pad, uint32_t* keys_out, uint32_t* v
                             const uint32_t* list, int64_t count, int64_t keys, int k, bool f32, hipStream_t s,
                             LaunchHook* hook);
 
+// Segmented top-k of 32-bit keys (topk_segs.hip): the k best keys of every
+// segment and their positions inside it, into row `segment` of nseg x k outputs;
+// records, maps and order as topk_pass, classes and lists as the segmented
+// sorts with key_bytes = 8 (topk_segs_plan.h says what runs per class).
+//   topk_segs_tile    one class lr = 5..13, keys -> outputs: the `count` segments
+//                     of `list`, 2^(13 - lr) per LDS tile; slots j < min(len, k)
+//                     of a row are written.  One KIND_TILE_SORT record;
+//   topk_segs_pieces  one class cls >= 14, keys -> candidates: cand[(r P + piece)
+//                     k + j], P = 2^(cls - 13), r the segment's place in `list`:
+//                     `count` uniform rows of P k records for topk_pass (k <=
+//                     2^10).  One KIND_TILE_SORT record;
+//   topk_segs_last    a long class's last pass p (p.npieces == 1), records ->
+//                     outputs: row r of `count` rows of p.m_in records goes to
+//                     row list[r] of the outputs.  One KIND_TILE_SORT record;
+//   topk_segs_fill    slots [len, k) of every row with len < k: the index
+//                     0xFFFFFFFF and (keys_out given) the fill key, the unmapped
+//                     all-ones key.  Reads only off[0..nseg].  One KIND_OTHER record.
+// keys_out may be null.  No output may overlap an input.  Element alignment.
+hipError_t topk_segs_tile(const uint32_t* keys_in, uint32_t* keys_out, uint32_t* idx_out, const int64_t* off,
+                          const uint32_t* list, int64_t count, int lr, int64_t keys, int64_t k, bool f32,
+                          bool largest, hipStream_t s, LaunchHook* hook);
+hipError_t topk_segs_pieces(const uint32_t* keys_in, uint64_t* cand, const int64_t* off, const uint32_t* list,
+                            int64_t count, int cls, int64_t keys, int64_t k, bool f32, bool largest, hipStream_t s,
+                            LaunchHook* hook);
+hipError_t topk_segs_last(const TopkPass& p, const uint64_t* recs_in, uint32_t* keys_out, uint32_t* idx_out,
+                          const uint32_t* list, int64_t count, int64_t k, bool f32, bool largest, hipStream_t s,
+                          LaunchHook* hook);
+hipError_t topk_segs_fill(const int64_t* off, int64_t nseg, int64_t k, uint32_t* keys_out, uint32_t* idx_out,
+                          bool f32, bool largest, hipStream_t s, LaunchHook* hook);
+
 // Counter-based SplitMix64 keys for global indices [g0, g0+n) (bench/test input).
 hipError_t fill_splitmix_u32(uint32_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);
 hipError_t fill_splitmix_u64(uint64_t* out, int64_t n, uint64_t seed, int64_t g0, hipStream_t s);

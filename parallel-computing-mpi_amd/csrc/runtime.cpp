@@ -8,6 +8,7 @@
 #include "misort.h"
 #include "misort_topk.h"
 #include "misort_segments_pairs.h"
+#include "misort_topk_segments.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -32,6 +33,7 @@
 #include "kernels.h"
 #include "segs_class.h"
 #include "topk_plan.h"
+#include "topk_segs_plan.h"
 
 namespace {
 
@@ -2476,6 +2478,156 @@ int misort_local_sort_segments_pairs(misort_ctx* c, int key_dtype, const void* k
             return fail(MISORT_E_HIP, "misort::unpad_segs_pairs (class %d): %s", k, hipGetErrorString(e));
     }
     return MISORT_OK;
+}
+
+// Segmented top-k (topk_segs.hip): misort_local_sort_segments_pairs step for
+// step up to the class lists -- the count kernel with 8-byte classes, the one
+// fetch of its header, the refusals, the scatter -- then what topk_segs_plan.h
+// says per class: a fill of the short rows, one tile launch per class up to the
+// tile, and for every longer class, one at a time, the pieces' candidates, the
+// row-wise top-k's passes over them and a last pass into the segments' rows.
+// The candidates alternate between rowpad and pong as in misort_local_topk_rows.
+int misort_local_topk_segments(misort_ctx* c, int key_dtype, const void* keys_in, void* keys_out, void* idx_out,
+                               int64_t n, const int64_t* offsets, int64_t nseg, int64_t k, int largest,
+                               void* stream) {
+    if (!c) return fail(MISORT_E_INVALID, "null ctx");
+    if (!valid_pair_dtype(key_dtype))
+        return fail(MISORT_E_INVALID, "local_topk_segments takes MISORT_U32 or MISORT_F32 keys, got %d", key_dtype);
+    if (n < 0 || nseg < 0 || nseg > 0x7FFFFFFFll || k < 0)
+        return fail(MISORT_E_INVALID, "bad local_topk_segments arguments (0 <= n, 0 <= nseg <= 2^31 - 1, 0 <= k)");
+    if (n > (INT64_MAX >> 5))
+        return fail(MISORT_E_INVALID, "local_topk_segments: %lld keys are too many", (long long)n);
+    if (k == 0 || nseg == 0) return MISORT_OK;  // no array is looked at
+    if (!misort::topk_segs_k_ok(k))
+        return fail(MISORT_E_INVALID,
+                    "local_topk_segments: k = %lld: 1 <= k <= 2^%d is needed (sort the segments with "
+                    "misort_local_sort_segments_pairs and take the first k of each)",
+                    (long long)k, misort::TOPK_LT);
+    const uint64_t in_bytes = (uint64_t)n * 4, out_bytes = (uint64_t)nseg * (uint64_t)k * 4,
+                   off_bytes = ((uint64_t)nseg + 1) * 8;
+    // a tile stores its segments' rows while other tiles still read their keys and the offsets
+    if (ranges_overlap(keys_out, out_bytes, keys_in, in_bytes) || ranges_overlap(idx_out, out_bytes, keys_in, in_bytes))
+        return fail(MISORT_E_INVALID, "local_topk_segments: an output overlaps d_keys_in");
+    if (ranges_overlap(keys_out, out_bytes, offsets, off_bytes) || ranges_overlap(idx_out, out_bytes, offsets, off_bytes))
+        return fail(MISORT_E_INVALID, "local_topk_segments: an output overlaps d_offsets");
+    if (ranges_overlap(keys_out, out_bytes, idx_out, out_bytes))
+        return fail(MISORT_E_INVALID, "local_topk_segments: d_keys_out overlaps d_idx_out");
+    if (!idx_out || !offsets || (n > 0 && !keys_in)) return fail(MISORT_E_INVALID, "bad local_topk_segments arguments");
+    if ((uintptr_t)offsets & 7) return fail(MISORT_E_INVALID, "local_topk_segments: d_offsets is not 8-byte aligned");
+    if (((uintptr_t)keys_in | (uintptr_t)keys_out | (uintptr_t)idx_out) & 3)
+        return fail(MISORT_E_INVALID, "local_topk_segments: an array is not 4-byte aligned");
+    hipStream_t s = pick(c, stream);
+
+    int rc = c->segs.ensure(misort::SEG_LIST_BYTES + (size_t)nseg * sizeof(uint32_t));
+    if (rc) return rc;
+    char* hdr = (char*)c->segs.p;
+    uint32_t* lists = (uint32_t*)(hdr + misort::SEG_LIST_BYTES);
+    HIPCHK(hipMemsetAsync(hdr, 0, misort::SEG_H_WORDS * 8, s));
+    hipError_t e = misort::seg_count(offsets, nseg, n, 8, hdr, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::seg_count: %s", hipGetErrorString(e));
+    int64_t h[misort::SEG_H_WORDS];
+    if ((rc = fetch(c, s, {{h, hdr, misort::SEG_H_FETCH * 8}}))) return rc;  // the call's one host wait
+    if (h[misort::SEG_H_BAD] != 0)
+        return fail(MISORT_E_INVALID,
+                    "local_topk_segments: malformed offsets: %lld of %lld segments, the first at index %lld "
+                    "(0 <= offsets[i] <= offsets[i + 1] <= n = %lld is needed); nothing was written",
+                    (long long)h[misort::SEG_H_BAD], (long long)nseg, (long long)~h[misort::SEG_H_BAD_AT], (long long)n);
+    // the class lists, class after class; what topk_segs_plan.h refuses of the classes that occur
+    const int lt = misort::TOPK_LT;
+    int64_t base[misort::SEG_CLASSES], listed = 0;
+    for (int cl = 0; cl < misort::SEG_CLASSES; ++cl) {
+        base[cl] = listed;
+        listed += h[misort::SEG_H_COUNT + cl];
+    }
+    if (listed > nseg) return fail(MISORT_E_INTERNAL, "local_topk_segments: the count kernel listed too many segments");
+    for (int pass = 0; pass < 2; ++pass)  // a too long segment first, then k
+        for (int cl = lt + 1; cl < misort::SEG_CLASSES; ++cl) {
+            const int64_t count = h[misort::SEG_H_COUNT + cl];
+            if (count == 0) continue;
+            const misort::TopkSegsRefusal why = misort::topk_segs_class_refusal(cl, k);
+            if (pass == 0 && why == misort::TOPK_SEGS_TOO_LONG)
+                return fail(MISORT_E_INVALID,
+                            "local_topk_segments: %lld segments are longer than 2^31 keys (a position must stay "
+                            "below 2^31); nothing was written",
+                            (long long)count);
+            if (pass == 1 && why != misort::TOPK_SEGS_OK)
+                return fail(MISORT_E_INVALID,
+                            "local_topk_segments: k = %lld with %lld segments longer than 2^%d keys: such segments "
+                            "take k <= %lld (use misort_local_sort_segments_pairs' argsort); nothing was written",
+                            (long long)k, (long long)count, lt, (long long)misort::TOPK_K_LONG_MAX);
+        }
+    const bool f32 = key_dtype == MISORT_F32, big = largest != 0;
+    const uint32_t* ki = (const uint32_t*)keys_in;
+    uint32_t* ko = (uint32_t*)keys_out;
+    uint32_t* io = (uint32_t*)idx_out;
+    if (listed > 0) {
+        if ((rc = h2d(c, hdr + misort::SEG_H_CURSOR * 8, base, sizeof(base), s))) return rc;
+        e = misort::seg_scatter(offsets, nseg, 8, hdr + misort::SEG_H_CURSOR * 8, lists, listed, s, hook(c));
+        if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::seg_scatter: %s", hipGetErrorString(e));
+    }
+    // (both candidate buffers before the first key kernel: growing one frees it, which waits for the device)
+    misort::TopkPass plan[misort::TOPK_MAX_PASSES];
+    size_t cand0 = 0, cand1 = 0;
+    for (int cl = lt + 1; cl < misort::TOPK_SEGS_CLASS_END; ++cl) {
+        const int64_t count = h[misort::SEG_H_COUNT + cl];
+        if (count == 0) continue;
+        const int np = misort::topk_segs_class_plan(cl, k, plan, misort::TOPK_MAX_PASSES);
+        if (np < 2 || np > misort::TOPK_MAX_PASSES) return fail(MISORT_E_INTERNAL, "local_topk_segments: no plan");
+        cand0 = std::max(cand0, (size_t)count * (size_t)plan[0].m_out * 8);
+        if (np > 2) cand1 = std::max(cand1, (size_t)count * (size_t)plan[1].m_out * 8);
+    }
+    if (cand0 > 0 && (rc = c->rowpad.ensure(cand0))) return rc;
+    if (cand1 > 0 && (rc = c->pong.ensure(cand1))) return rc;
+    e = misort::topk_segs_fill(offsets, nseg, k, ko, io, f32, big, s, hook(c));
+    if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::topk_segs_fill: %s", hipGetErrorString(e));
+    if (listed == 0) return MISORT_OK;  // every segment is empty
+    for (int lr = misort::SEG_LR_MIN; lr <= lt; ++lr) {
+        const int64_t count = h[misort::SEG_H_COUNT + lr], keys = h[misort::SEG_H_KEYS + lr];
+        if (count == 0) continue;
+        e = misort::topk_segs_tile(ki, ko, io, offsets, lists + base[lr], count, lr, keys, k, f32, big, s, hook(c));
+        if (e != hipSuccess) return fail(MISORT_E_HIP, "misort::topk_segs_tile (class %d): %s", lr, hipGetErrorString(e));
+    }
+    // a class's last pass has read its candidates before the next class's first pass rewrites them: one stream
+    for (int cl = lt + 1; cl < misort::TOPK_SEGS_CLASS_END; ++cl) {
+        const int64_t count = h[misort::SEG_H_COUNT + cl], keys = h[misort::SEG_H_KEYS + cl];
+        if (count == 0) continue;
+        const uint32_t* list = lists + base[cl];
+        const int np = misort::topk_segs_class_plan(cl, k, plan, misort::TOPK_MAX_PASSES);
+        // pass i writes buffer i % 2: rowpad holds the first pass's candidates, pong the second's
+        e = misort::topk_segs_pieces(ki, (uint64_t*)c->rowpad.p, offsets, list, count, cl, keys, k, f32, big, s, hook(c));
+        if (e != hipSuccess)
+            return fail(MISORT_E_HIP, "misort::topk_segs_pieces (class %d): %s", cl, hipGetErrorString(e));
+        for (int i = 1; i < np; ++i) {
+            const uint64_t* src = (const uint64_t*)(i % 2 ? c->rowpad.p : c->pong.p);
+            if (i < np - 1)
+                e = misort::topk_pass(plan[i], nullptr, src, (uint64_t*)(i % 2 ? c->pong.p : c->rowpad.p), nullptr,
+                                      nullptr, count, k, f32, big, s, hook(c));
+            else
+                e = misort::topk_segs_last(plan[i], src, ko, io, list, count, k, f32, big, s, hook(c));
+            if (e != hipSuccess)
+                return fail(MISORT_E_HIP, "local_topk_segments: pass %d of %d (class %d): %s", i + 1, np, cl,
+                            hipGetErrorString(e));
+        }
+    }
+    return MISORT_OK;
+}
+
+int misort_topk_segments_plan(int64_t len, int64_t k, int* passes, int max_passes) {
+    if (max_passes > 0 && !passes) return fail(MISORT_E_INVALID, "null passes");
+    misort::TopkPass plan[misort::TOPK_MAX_PASSES];
+    const int np = misort::topk_segs_plan(len, k, plan, misort::TOPK_MAX_PASSES);
+    if (np < 0)
+        return fail(MISORT_E_INVALID,
+                    "topk_segments_plan: 1 <= k <= 2^%d and 0 <= len <= 2^31 are needed, and k <= %lld for len > 2^%d; "
+                    "got len = %lld, k = %lld",
+                    misort::TOPK_LT, (long long)misort::TOPK_K_LONG_MAX, misort::TOPK_LT, (long long)len, (long long)k);
+    for (int i = 0; i < np && i < max_passes; ++i) {
+        passes[4 * i] = (int)(uint32_t)plan[i].m_in;  // 2^31: its unsigned 32-bit pattern
+        passes[4 * i + 1] = plan[i].lr;
+        passes[4 * i + 2] = (int)plan[i].npieces;
+        passes[4 * i + 3] = (int)plan[i].m_out;
+    }
+    return np;
 }
 
 int misort_segment_class(int64_t len, int key_bytes) {

@@ -20,7 +20,7 @@ __all__ = [
     "U32", "U64", "F64", "F32", "MisortError", "NotPowerOfTwo", "NativeLibraryMissing",
     "library_path", "lib", "Context", "Group", "block_sizes", "schedule", "tile_log2", "plan",
     "sample_indices", "exchange_count", "set_shared_gpu_env", "rows_plan",
-    "segment_class", "topk_plan",
+    "segment_class", "topk_plan", "topk_segments_plan",
 ]
 
 U32, U64, F64 = 0, 1, 2
@@ -89,6 +89,8 @@ def lib():
         "misort_topk_plan": ([i64, i64, ctypes.POINTER(i32), i32], i32),
         "misort_local_sort_segments": ([vp, i32, vp, vp, i64, vp, i64, vp], i32),
         "misort_local_sort_segments_pairs": ([vp, i32, vp, vp, vp, vp, i64, vp, i64, vp], i32),
+        "misort_local_topk_segments": ([vp, i32, vp, vp, vp, i64, vp, i64, i64, i32, vp], i32),
+        "misort_topk_segments_plan": ([i64, i64, ctypes.POINTER(i32), i32], i32),
         "misort_segment_class": ([i64, i32], i32),
         "misort_merge_split": ([vp, i32, vp, i64, vp, i64, vp, i32, vp], i32),
         "misort_merge_split_tail": ([vp, i32, vp, i64, vp, i64, i32, vp], i32),
@@ -217,6 +219,21 @@ def topk_plan(cols, k):
     np_ = _check(lib().misort_topk_plan(cols, k, None, 0))
     buf = (ctypes.c_int32 * (4 * max(np_, 1)))()
     _check(lib().misort_topk_plan(cols, k, buf, np_))
+    # m_in reaches 2^31: stored as its unsigned 32-bit pattern
+    return [(buf[4 * i] & 0xFFFFFFFF, buf[4 * i + 1], buf[4 * i + 2], buf[4 * i + 3]) for i in range(np_)]
+
+
+def topk_segments_plan(len, k):
+    """The passes of Context.topk_segments for ONE segment of ``len`` keys:
+    ``[(m_in, LR, npieces, m_out)]`` as topk_plan gives them.  ``len == 0``: no
+    pass (the fill alone writes the row); ``len <= 2^13``: one pass with
+    ``LR = max(ceil_log2(len), 5)`` and ``m_out = min(len, k)``; longer: the
+    passes of ``topk_plan(2^ceil_log2(len), k)``.  A (len, k) that the call
+    refuses (k outside 1..2^13, len above 2^31, k > 1024 with len > 2^13) is a
+    MisortError (code -1)."""
+    np_ = _check(lib().misort_topk_segments_plan(len, k, None, 0))
+    buf = (ctypes.c_int32 * (4 * max(np_, 1)))()
+    _check(lib().misort_topk_segments_plan(len, k, buf, np_))
     # m_in reaches 2^31: stored as its unsigned 32-bit pattern
     return [(buf[4 * i] & 0xFFFFFFFF, buf[4 * i + 1], buf[4 * i + 2], buf[4 * i + 3]) for i in range(np_)]
 
@@ -778,6 +795,71 @@ class Context:
         _check(lib().misort_local_topk_rows(self._h, dt, _ptr(keys), _ptr(values) if with_values else None,
                                             _ptr(indices), rows, cols, k, 1 if largest else 0,
                                             self._stream(stream)))
+        return values, indices
+
+    def topk_segments(self, keys, offsets, k, largest=True, out_values=None, out_indices=None, stream=None):
+        """The k largest (``largest=True``) or smallest keys of every segment of
+        the 1-D contiguous tensor ``keys`` and their positions inside the
+        segment: ``(values, indices)`` of shape ``(nseg, k)``, row i for segment
+        i, the keys ``[offsets[i], offsets[i + 1])``.  ``offsets`` is as in
+        sort_segments: a 1-D contiguous int64 tensor on the keys' device with at
+        least one element, non-decreasing, within [0, keys.numel()]; empty
+        segments are allowed and keys outside the segments are ignored.  Keys,
+        order and ties are topk_rows': u32 (uint32/int32 storage, compared
+        unsigned) or float32 in the total order of the bit patterns, each row
+        sorted best first, equal keys in ascending position order in both
+        directions, every real value bit-exact.  ``indices`` are the positions
+        argsort_segments returns, in the storage of argsort_rows (like u32
+        keys, int32 for float keys).
+
+        Fill: a segment shorter than k (an empty one included) leaves the slots
+        ``j >= len`` of its row with index 0xFFFFFFFF (-1 in int32 storage; a
+        real position is below 2^31, so it marks absence) and the last key of
+        the direction's order: u32 0xFFFFFFFF (smallest) or 0 (largest),
+        float32 bit pattern 0x7FFFFFFF (smallest) or 0xFFFFFFFF (largest).  A
+        real key may equal the fill key; only the index tells.
+
+        ``1 <= k <= 2^13``, ``k <= 1024`` if any segment is longer than 2^13
+        keys, and no segment may be longer than 2^31 keys (else MisortError,
+        code -1, nothing written); ``k == 0`` gives empty outputs.  The outputs
+        must not overlap the keys, the offsets or each other (MisortError, code
+        -1); the inputs are left unchanged.
+
+        The call waits once on its stream: the host waits for a kernel that
+        validates and counts the segments (so the call cannot be captured in a
+        graph); malformed offsets are a MisortError (code -1) naming the first
+        bad index, and nothing is written then.  Wrong dtypes raise TypeError;
+        wrong shapes, non-contiguous tensors, a negative k, a too-small output
+        and a tensor on another device ValueError.  ``topk_segments_plan(len,
+        k)`` tells the passes of one segment."""
+        return self._topk_segments("topk_segments", keys, offsets, k, largest, True, out_values, out_indices, stream)
+
+    def topk_segments_indices(self, keys, offsets, k, largest=True, out=None, stream=None):
+        """The ``indices`` of topk_segments alone: no keys are written.  The
+        fill index of a segment shorter than k is 0xFFFFFFFF (-1 in int32
+        storage); the call waits once on its stream, as topk_segments does."""
+        return self._topk_segments("topk_segments_indices", keys, offsets, k, largest, False, None, out, stream)[1]
+
+    def _topk_segments(self, what, keys, offsets, k, largest, with_values, out_values, out_indices, stream):
+        import torch
+        dt = _pair_key_dtype(keys)
+        nseg = self._segments_pairs_check(what, keys, offsets, out_values=out_values, out_indices=out_indices)
+        if not keys.is_contiguous():
+            raise ValueError(f"{what} needs a contiguous tensor, got strides {tuple(keys.stride())}")
+        k = int(k)
+        if k < 0:
+            raise ValueError(f"{what}: negative k {k}")
+        if out_values is not None and out_values.dtype != keys.dtype:
+            raise TypeError(f"out_values is {out_values.dtype}, the keys are {keys.dtype}")
+        _pair_values(out_indices, "out_indices")
+        shape, n = (nseg, k), nseg * k
+        values = self._topk_out("out_values", out_values, keys, keys.dtype, shape, n) if with_values else None
+        indices = self._topk_out("out_indices", out_indices, keys,
+                                 keys.dtype if _u32_storage(keys) else torch.int32, shape, n)
+        _check(lib().misort_local_topk_segments(self._h, dt, _ptr(keys) if keys.numel() else None,
+                                                _ptr(values) if with_values else None, _ptr(indices),
+                                                keys.numel(), _ptr(offsets), nseg, k, 1 if largest else 0,
+                                                self._stream(stream)))
         return values, indices
 
     def sort_pairs64(self, keys, values, out_keys=None, out_values=None, n=None, stream=None):
